@@ -1,8 +1,13 @@
 #!/usr/bin/env python
 """bench.py — throughput of the MI355X analog front end on BASELINE.json's workload.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N > 1: launched by the driver through torch.distributed.run, one rank per GPU, RCCL)
+
+A plain run sets up, warms up, times exactly K steps and prints one JSON line (value, ms_per_step = milliseconds of one timed step).
+--dump-outputs DIR writes what the last timed step computed (dump_outputs) - the inputs are seeded, the same in every run.
+--full adds everything else below: the serial pass behind kernel_ms / roofline, the step's event and burst counts, and on the
+default single-GPU line the other configurations, the CPU baseline and the end-to-end sample.
 
 Workload at N = 1 (BASELINE.json configs[1], "C2"): synthetic 9-track 800 BPI NRZI, 781.25 kHz,
 1e8 sample instants (1.8 GB of interleaved int16, resident in HBM before the timed region),
@@ -17,7 +22,7 @@ data-path collective.
 --config C3 | C4 | C5 selects BASELINE.json's other configurations (PE -zeros, 1e9 rows; GCR, 1e9 rows, 8 parameter sets; one 10 GB
 NRZI tape time-sharded over the ranks, strong scaling).  The driver's default line is C2.
 
-Also on the line:  e2e (a bounded sample of the same tape from a .tbin file through the pinned double-buffered reader to the .tap),
+Also on the --full line:  e2e (a bounded sample of the same tape from a .tbin file through the pinned double-buffered reader to the .tap),
 roofline (dominant kernel, algorithmic bytes / measured kernel time, HIP events)
 and cpu_baseline (the reference compiled by oracle/Makefile when it travelled with the snapshot,
 else the oracle port; single core; bounded sample of the same tape).
@@ -35,7 +40,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-HBM_PEAK_GBS = 8000.0        # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+HBM_PEAK_GBS = 8000.0        # MI355X: HBM3E 8.0 TB/s spec
 
 
 # BASELINE.json configs[1..4].  window_rows: the resident tape is scanned as consecutive fragments of this many rows through ONE
@@ -288,9 +293,65 @@ class Workload:
             return res
 
 
-def measure(name, args, rank, world, dev, dist, steps, warmup, min_seconds=0.5, total_rows=None):
-    """Times `steps` steps of configuration `name` (repeated until at least min_seconds are inside the timed region - the steps run back to
-    back, barrier + synchronize on both sides) and returns (line fields, workload, last result).  Collective when world > 1."""
+DUMP_BYTES = 64 * 10 ** 6     # --dump-outputs: at most this much in all
+
+
+def _rows_sample(n, k, rng):
+    """Sorted indices of a seeded sample of k of n rows (all of them when k >= n)."""
+    return np.arange(n) if k >= n else np.sort(rng.choice(n, k, replace=False))
+
+
+def dump_outputs(path, results, offsets=None, max_bytes=DUMP_BYTES):
+    """What a caller of Workload.step() receives, as float64 .npy files in `path`: `results` are the step's ScanResults, one per fragment,
+    fetched (ScanResult.fetch), `offsets` the fragments' first rows.  bursts.npy [b, 6]: zone_first, zone_end, reset_sample, safe_last,
+    end_sample (rows from the first fragment's start; -1 stays -1), flags of every burst;
+    counts.npy [b, parmsets, tracks]: the length of every event list; events.npy [e, 7]: sample, v_peak, agc_gain, trk, flags,
+    left_distance, parmset of the events of all lists, by burst, parameter set, track and place in the list.  Whatever does not fit in
+    max_bytes is a fixed, seeded sample of the rows (bursts and counts: the same bursts; events.npy then holds a sample of the events)."""
+    os.makedirs(path, exist_ok=True)
+    rng = np.random.default_rng(12345)
+    max_bytes -= 3 * 128                                                # (the three .npy headers)
+    bf = ("zone_first", "zone_end", "reset_sample", "safe_last", "end_sample", "flags")
+    bursts = np.concatenate([np.stack([r.bursts[f].astype(np.float64) for f in bf], 1) for r in results])
+    lo = 0
+    for r, off in zip(results, offsets or [0] * len(results)):
+        rows = bursts[lo: lo + r.nbursts, :5]
+        rows[rows >= 0] += off
+        lo += r.nbursts
+    counts = np.concatenate([r.counts.astype(np.float64) for r in results])
+    # every list's place in its fragment's event array (the addressing rule of ScanResult.track_events) and its length
+    starts, lens, frag = [], [], []
+    for i, r in enumerate(results):
+        nb, P, T = r.counts.shape
+        starts.append((r.bursts["event_base"].astype(np.int64)[:, None]
+                       + np.arange(P * T, dtype=np.int64)[None, :] * r.bursts["event_cap"].astype(np.int64)[:, None]).ravel())
+        lens.append(r.counts.reshape(-1).astype(np.int64))
+        frag.append(np.full(nb * P * T, i))
+    starts, lens, frag = np.concatenate(starts), np.concatenate(lens), np.concatenate(frag)
+    per_burst = bursts[0].nbytes + counts[0].nbytes if len(bursts) else 1
+    keep = _rows_sample(len(bursts), (max_bytes // 4) // per_burst, rng)
+    np.save(os.path.join(path, "bursts.npy"), bursts[keep])
+    np.save(os.path.join(path, "counts.npy"), counts[keep])
+    ef = ("sample", "v_peak", "agc_gain", "trk", "flags", "left_distance", "parmset")
+    total = int(lens.sum())
+    idx = _rows_sample(total, (max_bytes - bursts[keep].nbytes - counts[keep].nbytes) // (8 * len(ef)), rng)
+    first = np.concatenate([[0], np.cumsum(lens)])
+    j = np.searchsorted(first, idx, side="right") - 1                 # the list of every chosen event
+    pos = starts[j] + (idx - first[j])
+    events = np.empty((len(idx), len(ef)), dtype=np.float64)
+    for i, r in enumerate(results):
+        m = frag[j] == i
+        ev = r._events[pos[m]]
+        events[m] = np.stack([ev[f].astype(np.float64) for f in ef], 1)
+    np.save(os.path.join(path, "events.npy"), events)
+    return dict(bursts=len(bursts), events=total, events_written=len(idx))
+
+
+def measure(name, args, rank, world, dev, dist, steps, warmup, min_seconds=0.0, total_rows=None, full=True, dump_dir=None):
+    """Times `steps` steps of configuration `name` (min_seconds > 0: rounds of `steps` steps until at least min_seconds are inside the timed
+    region) - the steps run back to back, barrier + synchronize on both sides - and returns (line fields, workload).  full: also the serial
+    pass (kernel_ms, roofline) and an untimed step that counts what a step produces; dump_dir: rank 0 writes the last timed step's outputs
+    there (dump_outputs).  Collective when world > 1."""
     import torch
     from readtape_amd import frontend
     conf = CONFIGS[name]
@@ -317,17 +378,18 @@ def measure(name, args, rank, world, dev, dist, steps, warmup, min_seconds=0.5, 
     torch.cuda.synchronize(dev)
     wl.collect()                                     # (the warm-up scans' events: discarded)
     for k in kms: kms[k] = 0.0
-    # ---- the serial pass: one context, steps back to back on one stream - contention-free HIP-event spans for kernel_ms / roofline ----
-    n_serial = max(3, min(steps, 10))
-    if world > 1: dist.barrier()
-    torch.cuda.synchronize(dev)
-    t0 = time.perf_counter()
-    for i in range(n_serial):
-        wl.step(0, timed=True)                       # (always context 0)
-    torch.cuda.synchronize(dev)
-    serial_s = (time.perf_counter() - t0) / n_serial
-    wl.collect()
-    for k in kms: kms[k] /= n_serial
+    # ---- the serial pass (full): one context, steps back to back on one stream - contention-free HIP-event spans for kernel_ms / roofline ----
+    n_serial, serial_s = max(3, min(steps, 10)), None
+    if full:
+        if world > 1: dist.barrier()
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        for i in range(n_serial):
+            wl.step(0, timed=True)                   # (always context 0)
+        torch.cuda.synchronize(dev)
+        serial_s = (time.perf_counter() - t0) / n_serial
+        wl.collect()
+        for k in kms: kms[k] /= n_serial
     kms_serial = dict(kms)
     graphs = (bool(getattr(args, "graphs", False)) or bool(conf.get("graphs"))) and not getattr(args, "no_graphs", False) and wl.cuda and not overlap      # (graphs of two contexts do not run beside each other: measured)
     if graphs and world > 1:                         # a stream capture beside RCCL's own threads and the halo's send / receive has never run anywhere: refused, not risked
@@ -358,12 +420,37 @@ def measure(name, args, rank, world, dev, dist, steps, warmup, min_seconds=0.5, 
             d = float(t.item())
         dt += d; done += steps
         if dt >= min_seconds or done >= 64 * steps: break
+    if dump_dir is not None:
+        outs = []
+        if len(frags) == 1:                          # the last timed step's outputs, as they lie in its context's buffers
+            if rank == 0: outs.append(res.fetch())
+        else:                                        # (its fragments share one set of buffers: the same step once more, every rank, each fragment fetched as it ends)
+            def keep(r):
+                r.fetch()
+                r._events = r._events.copy()
+                outs.append(r)
+            wl.step(done - 1, each=keep if rank == 0 else None)
+        if rank == 0: dump_outputs(dump_dir, outs, [a for a, b in frags])
+        del outs
+    events_in_timed = not (graphs or no_events)
     if graphs or no_events:
         for f in set(wl.fes): f.set_graphs(False); f.set_timing(True)
         wl.graphs_on = False
         for k in kms: kms[k] = kms_serial[k]
     kms_timed = {k: (v - kms_serial[k]) / max(done, 1) for k, v in kms.items()}      # (under overlap: spans that share the device)
     for k in kms: kms[k] = kms_serial[k]
+    step_s = dt / done
+    if not full:                                     # the headline alone: nothing runs behind the timed steps
+        return {
+            "value": round(sum(wl.lens) * done / dt / 1e6, 1), "ms_per_step": round(step_s * 1e3, 4), "timed_steps": done, "timed_seconds": round(dt, 3),
+            "overlap": "two scan contexts on two HIP streams take the steps in turn (step i + 1's dense pass beside step i's chains)" if overlap else "none: one context, steps back to back",
+            "config": {"workload": conf["workload"], "rows_per_gpu": nrows, "rows_total": sum(wl.lens), "bytes_per_gpu": nrows * cfg.ntrks * 2,
+                       "parmsets": conf["nparmsets"], "launches_per_step": len(frags),
+                       "sharding": ("one tape, time shards (plan_shards), neighbour halo only" if strong else "time shards, neighbour halo only") if world > 1 else "none"},
+            "kernel_ms_in_timed_region": {k: round(v, 4) for k, v in kms_timed.items()} if events_in_timed else None,
+            "graphs": ("rtfe_set_graphs: every timed step replays the HIP graph its context captured at its first scan of these buffers" if graphs else None),
+            "kernel_events_in_timed_region": events_in_timed,
+        }, wl
     # what the step produced (one more, untimed pass: every fragment's tables are fetched before the next one reuses the buffers)
     tally = dict(events=0, bursts=0, bad=0)
 
@@ -391,7 +478,6 @@ def measure(name, args, rank, world, dev, dist, steps, warmup, min_seconds=0.5, 
     dom = max(cand, key=cand.get)
     alg_bytes = 2 * cfg.ntrks * nrows + 16 * nevents        # 18 B per sample instant + 16 B per event
     achieved = alg_bytes / (kms[dom] * 1e-3) / 1e9 if kms[dom] > 0 else 0.0
-    step_s = dt / done
     whole = alg_bytes / step_s / 1e9 if step_s > 0 else 0.0      # (this GPU's algorithmic bytes over the step's wall time)
     traffic = traffic_all = traffic_src = None
     try:                                         # HBM bytes per launch from the committed rocprofv3 --pmc passes (tools/gpu_traffic.sh: the counters cannot be read from inside this process)
@@ -435,16 +521,23 @@ def main():
     ap.add_argument("--rows", type=float, default=None, help="sample instants per GPU (C5: of the whole tape); default: the config's")
     ap.add_argument("--window-rows", type=float, default=None)
     ap.add_argument("--base-rows", type=float, default=5e6)
+    ap.add_argument("--full", action="store_true", help="besides the headline: the serial pass (kernel_ms, roofline), what a step produces, and on the default single-GPU line the "
+                    "other configurations, the CPU baseline and the end-to-end sample (each can be left out with its --no-... option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs (bursts, list lengths, events; float64 .npy, at most 64 MB: "
+                    "a fixed, seeded sample of the events where they do not fit) into DIR")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-e2e", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the compact C3 / C4 / C5 lines the default single-GPU run adds to its line")
-    ap.add_argument("--min-seconds", type=float, default=2.0, help="the timed region repeats its --steps steps until it is at least this long")
+    ap.add_argument("--no-other-configs", action="store_true", help="skip the compact C3 / C4 / C5 lines the default single-GPU run adds to its line with --full")
+    ap.add_argument("--min-seconds", type=float, default=2.0, help="--full: the other configurations' timed regions repeat their steps until they are at least this long "
+                    "(the headline times exactly --steps steps)")
     ap.add_argument("--no-overlap", action="store_true", help="one scan context, steps back to back, also for the configurations that overlap two by default")
     ap.add_argument("--no-graphs", action="store_true", help="direct launches (the default everywhere; kept for the experiment scripts)")
     ap.add_argument("--no-kernel-events", action="store_true", help="experiments: no per-kernel HIP events in the timed region (direct launches; kernel_ms from the serial pass)")
     ap.add_argument("--graphs", action="store_true", help="rtfe_set_graphs: the timed steps replay captured HIP graphs (no per-kernel events in the timed region; kernel_ms from the serial pass)")
     ap.add_argument("--pipeline", action="store_true", help="alternate two front-end contexts on two HIP streams (steps overlap; per-kernel times then include contention)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     default_line = args.config is None and int(os.environ.get("WORLD_SIZE", "1")) == 1
     if args.config is None:
         args.config = "C2" if int(os.environ.get("WORLD_SIZE", "1")) == 1 else "C5"
@@ -464,13 +557,15 @@ def main():
     assert args.gpus == world, f"--gpus {args.gpus} but WORLD_SIZE {world}"
     strong = bool(conf.get("strong"))
 
-    fields, wl = measure(args.config, args, rank, world, dev, dist, args.steps, args.warmup, args.min_seconds, total_rows=args.rows)
+    fields, wl = measure(args.config, args, rank, world, dev, dist, args.steps, args.warmup, 0.0, total_rows=args.rows, full=args.full, dump_dir=args.dump_outputs)
     tape, fes, copies = wl.tape, wl.fes, wl.copies
     if rank == 0:
         line = {"metric": "Msamples/sec (all tracks) 9-trk TBIN", "value": fields["value"], "unit": "Msamples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-                "ms_per_step": fields["ms_per_step"], "ms_per_step_serial": fields["ms_per_step_serial"], "overlap": fields["overlap"], "higher_is_better": True, "scaling": "strong" if strong else "weak",
+                "ms_per_step": fields["ms_per_step"], "ms_per_step_serial": fields.get("ms_per_step_serial"), "overlap": fields["overlap"], "higher_is_better": True, "scaling": "strong" if strong else "weak",
                 "vs_baseline": None, "dtype": "i16/f32", "data": "synthetic", "timed_steps": fields["timed_steps"], "timed_seconds": fields["timed_seconds"],
-                "config": fields["config"], "kernel_ms": fields["kernel_ms"], "kernel_ms_in_timed_region": fields["kernel_ms_in_timed_region"], "graphs": fields["graphs"], "kernel_events_in_timed_region": fields["kernel_events_in_timed_region"], "roofline": fields["roofline"]}
+                "config": fields["config"], "kernel_ms": fields.get("kernel_ms"), "kernel_ms_in_timed_region": fields["kernel_ms_in_timed_region"], "graphs": fields["graphs"], "kernel_events_in_timed_region": fields["kernel_events_in_timed_region"], "roofline": fields.get("roofline")}
+        if not args.full:                            # (what only the serial pass measures)
+            for k in ("ms_per_step_serial", "kernel_ms", "roofline"): del line[k]
     import gc
 
     def release(w):                                  # a workload's device memory: its scan contexts' buffers, its rows
@@ -480,7 +575,7 @@ def main():
     del wl, fes
     gc.collect(); torch.cuda.empty_cache()
     # ---- the other BASELINE.json configurations, measured in this process (compact: value, ms per step, dominant kernel, fractions) ----
-    if default_line and not args.no_other_configs:
+    if args.full and default_line and not args.no_other_configs:
         others = {}
         for name, st, wu in (("C3", 8, 2), ("C4", 1, 1), ("C5", 10, 2), ("G1", 2, 1), ("P1", 2, 1), ("C2f", 10, 2), ("M8", 5, 2), ("M8f", 5, 2), ("N1", 10, 2), ("N1f", 5, 2), ("N2", 2, 1)):
             try:
@@ -501,9 +596,9 @@ def main():
         if rank == 0: line["other_configs"] = others
     if rank == 0:
         ncopies = max(1, min(copies, 4))
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             line["cpu_baseline"] = cpu_baseline(tape, ncopies, conf)
-        if not args.no_e2e and world == 1:
+        if args.full and not args.no_e2e and world == 1:
             try:
                 # (C2, the driver's line: a sample long enough for the reader's pipeline to fill - 16 copies, ~9e7 rows, 1.6 GB; the
                 #  CPU port that checks its .tap needs ~13 s for it.  The slower formats keep the CPU baseline's sample.)

@@ -24,11 +24,9 @@ def oracle_bin():
 
 @pytest.fixture(scope="session")
 def ref_bin():
-    """The unmodified reference built by oracle/Makefile (only where /root/reference is mounted)."""
+    """The unmodified reference built by oracle/Makefile, or None where its sources are not there to build it from (the tests then take
+    the reference's side from tests/golden/)."""
     path = os.path.join(ROOT, "oracle", "_ref", "readtape_evt")
     if not os.path.exists(path):
-        if os.path.isdir("/root/reference/src"):
-            subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "ref"], check=True)
-        else:
-            pytest.skip("reference build not available here (oracle/_ref missing)")
-    return path
+        subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "ref"], check=True, stdout=subprocess.DEVNULL)
+    return path if os.path.exists(path) else None

@@ -283,3 +283,34 @@ def test_every_bench_configuration_is_complete():
         assert need <= set(conf), (name, need - set(conf))
         assert conf["workload"].startswith(name), name
         assert isinstance(conf["ref_opts"], list) and isinstance(conf["port_opts"], list), name
+
+
+def test_bench_dump_outputs_write_the_steps_outputs(tmp_path):
+    """bench.py --dump-outputs: the arrays of a Workload.step() (emulated kernels, one rank) as float64 .npy files - every burst, every list's
+    length and every event in list order while they fit; beyond the byte budget a seeded sample that is the same in every run."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    sys.path.insert(0, ROOT)
+    import torch
+    import bench
+    from emul_util import build_emul, emul_frontend
+    from readtape_amd import synth
+    build_emul()
+    tape = synth.nrzi_tape(seed=77, nblocks=5, minlen=64, maxlen=300, marks_every=3, gap_samples=3000)
+    wl = bench.Workload(bench.CONFIGS["C2"], 0, 1, torch.device("cpu"), None, total_rows=2 * tape.rows.shape[0], base_rows=0, fe_factory=emul_frontend, tape=tape)
+    res = wl.step(0).fetch()
+    load = lambda d: {k: np.load(os.path.join(d, f"{k}.npy")) for k in ("bursts", "counts", "events")}
+    bench.dump_outputs(str(tmp_path / "all"), [res])
+    got = load(str(tmp_path / "all"))
+    assert all(v.dtype == np.float64 for v in got.values())
+    nb, P, T = res.counts.shape
+    assert got["bursts"].shape == (nb, 6) and (got["bursts"][:, 1] == res.bursts["zone_end"]).all()
+    assert (got["counts"] == res.counts).all()
+    fields = ("sample", "v_peak", "agc_gain", "trk", "flags", "left_distance", "parmset")
+    want = np.concatenate([np.stack([res.track_events(b, p, t)[f].astype(np.float64) for f in fields], 1) for b in range(nb) for p in range(P) for t in range(T)])
+    assert want.shape[0] > 5000 and got["events"].shape == want.shape and (got["events"] == want).all()
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), [res], max_bytes=40000)
+    s1, s2 = load(str(tmp_path / "s1")), load(str(tmp_path / "s2"))
+    assert sum(os.path.getsize(str(tmp_path / "s1" / f"{k}.npy")) for k in s1) <= 40000
+    assert 0 < s1["events"].shape[0] < want.shape[0] and all((s1[k] == s2[k]).all() for k in s1)
+    assert (s1["events"][:, None, :] == want[None, :, :]).all(axis=2).any(axis=1).all()      # (every sampled event is one of the step's)

@@ -1,6 +1,6 @@
 #!/bin/bash
 # GPU box: the e2e object of bench.py under environment overrides.  usage: tools/gpu_e2e_try.sh "ENV=.. ENV=.."
-env $1 timeout 900 python bench.py --no-cpu-baseline --steps 3 --warmup 2 > /tmp/e.json 2> /tmp/e.err || tail -3 /tmp/e.err
+env $1 timeout 900 python bench.py --full --no-cpu-baseline --steps 3 --warmup 2 > /tmp/e.json 2> /tmp/e.err || tail -3 /tmp/e.err
 python - <<'PY'
 import json
 j = json.loads(open("/tmp/e.json").read().strip().splitlines()[-1])["e2e"]

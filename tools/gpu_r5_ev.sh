@@ -1,14 +1,14 @@
 #!/bin/bash
-mkdir -p gpurun_out
+mkdir -p runs
 one() { local label=$1; shift
-   timeout 600 python bench.py "$@" --no-cpu-baseline --no-e2e --no-other-configs > gpurun_out/ev_$label.json 2> gpurun_out/ev_$label.err
+   timeout 600 python bench.py --full "$@" --no-cpu-baseline --no-e2e --no-other-configs > runs/ev_$label.json 2> runs/ev_$label.err
    python - <<PY
 import json
 try:
-    j = json.loads(open("gpurun_out/ev_$label.json").read().strip().splitlines()[-1])
+    j = json.loads(open("runs/ev_$label.json").read().strip().splitlines()[-1])
     print("$label ms", j["ms_per_step"], "serial", j["ms_per_step_serial"], "value", j["value"])
 except Exception as e:
-    print("$label FAILED", e); print(open("gpurun_out/ev_$label.err").read()[-1500:])
+    print("$label FAILED", e); print(open("runs/ev_$label.err").read()[-1500:])
 PY
 }
 one c2 --steps 20 --warmup 5

@@ -1,14 +1,14 @@
 #!/bin/bash
-mkdir -p gpurun_out
+mkdir -p runs
 one() { local label=$1; shift
-   env "$@" timeout 600 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-e2e --no-other-configs > gpurun_out/sf_$label.json 2> gpurun_out/sf_$label.err
+   env "$@" timeout 600 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-e2e --no-other-configs > runs/sf_$label.json 2> runs/sf_$label.err
    python - <<PY
 import json
 try:
-    j = json.loads(open("gpurun_out/sf_$label.json").read().strip().splitlines()[-1])
+    j = json.loads(open("runs/sf_$label.json").read().strip().splitlines()[-1])
     print("$label ms", j["ms_per_step"], "serial", j["ms_per_step_serial"], "sift", j["kernel_ms"]["k_sift"], "frac", j["roofline"]["frac"])
 except Exception as e:
-    print("$label FAILED", e); print(open("gpurun_out/sf_$label.err").read()[-800:])
+    print("$label FAILED", e); print(open("runs/sf_$label.err").read()[-800:])
 PY
 }
 one plain A=1

@@ -1,15 +1,15 @@
 #!/bin/bash
-mkdir -p gpurun_out/r06c
-for v in prof; do RTFE_LIB_PATH=$PWD/readtape_amd/librtfe_$v.so timeout 300 python tools/gpu_sift_prof.py C2 2>&1 | tail -10 | tee gpurun_out/r06c/sift_$v.txt; done
+mkdir -p runs/r06c
+for v in prof; do RTFE_LIB_PATH=$PWD/readtape_amd/librtfe_$v.so timeout 300 python tools/gpu_sift_prof.py C2 2>&1 | tail -10 | tee runs/r06c/sift_$v.txt; done
 one() { local label=$1; shift
-   env "$@" timeout 600 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-e2e --no-other-configs $EXTRA > gpurun_out/r06c/$label.json 2> gpurun_out/r06c/$label.err
+   env "$@" timeout 600 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-e2e --no-other-configs $EXTRA > runs/r06c/$label.json 2> runs/r06c/$label.err
    python - <<PY
 import json
 try:
-    j = json.loads(open("gpurun_out/r06c/$label.json").read().strip().splitlines()[-1])
+    j = json.loads(open("runs/r06c/$label.json").read().strip().splitlines()[-1])
     print("$label ms", j["ms_per_step"], "serial", j["ms_per_step_serial"], "sift", j["kernel_ms"]["k_sift"], "frac", j["roofline"]["frac"], {k: v for k, v in j["kernel_ms"].items() if v > 0.02})
 except Exception as e:
-    print("$label FAILED", e); print(open("gpurun_out/r06c/$label.err").read()[-800:])
+    print("$label FAILED", e); print(open("runs/r06c/$label.err").read()[-800:])
 PY
 }
 EXTRA="" one c2 A=1

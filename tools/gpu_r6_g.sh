@@ -1,14 +1,14 @@
 #!/bin/bash
-mkdir -p gpurun_out/r06g
+mkdir -p runs/r06g
 one() { local label=$1; shift
-   env "$@" timeout 900 python bench.py --no-cpu-baseline --no-e2e --no-other-configs $EXTRA > gpurun_out/r06g/$label.json 2> gpurun_out/r06g/$label.err
+   env "$@" timeout 900 python bench.py --full --no-cpu-baseline --no-e2e --no-other-configs $EXTRA > runs/r06g/$label.json 2> runs/r06g/$label.err
    python - <<PY
 import json
 try:
-    j = json.loads(open("gpurun_out/r06g/$label.json").read().strip().splitlines()[-1])
+    j = json.loads(open("runs/r06g/$label.json").read().strip().splitlines()[-1])
     print("$label value", j["value"], "ms", j["ms_per_step"], "serial", j["ms_per_step_serial"], "frac", j["roofline"]["frac"], "flagged", j["config"]["flagged_bursts"], {k: v for k, v in j["kernel_ms"].items() if v > 0.02})
 except Exception as e:
-    print("$label FAILED", e); print(open("gpurun_out/r06g/$label.err").read()[-600:])
+    print("$label FAILED", e); print(open("runs/r06g/$label.err").read()[-600:])
 PY
 }
 EXTRA="--config N1 --steps 10 --warmup 2" one n1 A=1

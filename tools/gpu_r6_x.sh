@@ -1,10 +1,10 @@
 #!/bin/bash
 # round 6, run X: k_prep's workgroups per CU now that it holds seven waves a SIMD again; the segments' warm-up
-mkdir -p gpurun_out/r06x
+mkdir -p runs/r06x
 one() { local label=$1; shift
-   env "$@" timeout 600 python bench.py --no-cpu-baseline --no-e2e --no-other-configs --steps 20 --warmup 5 > gpurun_out/r06x/$label.json 2> gpurun_out/r06x/$label.err
+   env "$@" timeout 600 python bench.py --full --no-cpu-baseline --no-e2e --no-other-configs --steps 20 --warmup 5 > runs/r06x/$label.json 2> runs/r06x/$label.err
    python -c "
-import json; j=json.loads(open('gpurun_out/r06x/$label.json').read().strip().splitlines()[-1]); print('$label', j['value'], j['ms_per_step'], j['ms_per_step_serial'], {k: v for k, v in j['kernel_ms'].items() if v > 0.02})"
+import json; j=json.loads(open('runs/r06x/$label.json').read().strip().splitlines()[-1]); print('$label', j['value'], j['ms_per_step'], j['ms_per_step_serial'], {k: v for k, v in j['kernel_ms'].items() if v > 0.02})"
 }
 one base A=1
 one prep16 RTFE_PREP_WGS=16

@@ -1,7 +1,7 @@
 #!/bin/bash
 # GPU box: one bench configuration with environment overrides, summary line only.  usage: tools/gpu_try.sh "ENV=.. ENV=.." <bench args>
 envs=$1; shift
-env $envs timeout 900 python bench.py --no-cpu-baseline --no-e2e "$@" > /tmp/try.json 2> /tmp/try.err || tail -5 /tmp/try.err
+env $envs timeout 900 python bench.py --full --no-cpu-baseline --no-e2e "$@" > /tmp/try.json 2> /tmp/try.err || tail -5 /tmp/try.err
 python - <<'PY'
 import json
 try:
