@@ -257,8 +257,12 @@ static int create_impl(const rtfe_config *c, rtfe_handle **out, int tile_overrid
       // differentiated: a restart differentiates against 0 and consecutive samples differ by up to 2q, and neither
       // may reach 0.2 V after the x0.4 x samples_per_bit scaling (src/readtape.c:1388)
       if (d.differentiate) quiet_v = 0.24f / (float)(d.samples_per_bit > 0 ? d.samples_per_bit : 1);
+      // P = the smallest c in 1 .. 32768 with volt(c) > 0.2 V (exact, same expression as the device's volt(); monotone in c, and
+      // volt(-c) = -volt(c)): a top confirms at v >= P, a bottom at v <= -P.  32768 counts: -32768 is a sample (and -invert turns it
+      // into +32768).  P = 32768 (maxvolts just under 0.2 V .. 0.2 V): only -32768 can confirm; P = 32769: nothing can.  Either way
+      // k_zeros' 16-bit lanes cannot hold P and k_decode's 32-bit mode takes the scan
       int code = 1;
-      while (code < 32767 && !((float)code / 32767 * c->maxvolts > 0.2f)) ++code;     // exact, same expression as the device's volt()
+      while (code <= 32768 && !((float)code / 32767 * c->maxvolts > 0.2f)) ++code;
       d.zc_peak_i = code; }
    if (d.differentiate && !d.find_zeros) {
       // peak detection on the differentiated signal (src/readtape.c:1383-1394): a zone is safe where the dead band

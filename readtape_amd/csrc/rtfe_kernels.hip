@@ -472,6 +472,11 @@ template <bool kGlobal> __device__ __forceinline__ auto zc_col(const Tile &tl, i
 
 __device__ __forceinline__ float volt(int i, float maxvolts) {      // src/readtape.c:1420
    return (float)i / 32767 * maxvolts; }
+// -invert negates the VOLTAGE: -volt(-32768) = volt(+32768), a code no int16 holds; load_tile's 16-bit negation leaves -32768 as it
+// was.  In an inverted tile nothing else negates to -32768, so there that code reads +32768 (rail = -32768; not inverted: rail = 1 << 30,
+// no sample).  The zero-crossing detectors read their samples through this; the peak path does not
+__device__ __forceinline__ int zc_rail(const DevCfg *cfg) { return cfg->invert ? -32768 : (1 << 30); }
+__device__ __forceinline__ int zc_code(int v, int rail) { return v == rail ? 32768 : v; }
 
 struct Walker {            // one per (parameter set, track); lives in registers
    // detector state
@@ -937,12 +942,12 @@ template <class WT> __device__ __forceinline__ void walk_zeros(WT &w, Ctx &cx, i
    const Tile &tl = cx.tile;
    const long long tile_end = tl.row0 + tl.nrows;
    if (limit > tile_end) limit = tile_end;
-   const int P = cfg->zc_peak_i;
+   const int P = cfg->zc_peak_i, rail = zc_rail(cfg);
    long long n = w.next;
    if (n <= w.start) n = w.start + 1;                              // row `start` only seeds the track (src/decoder.c:855-861)
    ZcState z; zc_load(z, w);
    for (; n < limit; ++n) {
-      const int v = tl.y(trk, n);
+      const int v = zc_code(tl.y(trk, n), rail);
       bool up = false; long long cross = 0;
       if (zc_row(z, v, n, P, up, cross)) {
          if (w.nevents < cx.cap) zc_event(cx, trk, w.nevents, n, v, up, cross);
@@ -1001,11 +1006,11 @@ __device__ __forceinline__ bool zc_same(const Zc32 &a, const Zc32 &b) {         
 // eight rows ahead of the steps that use them (pre = the batches already on their way, or nullptr): a batch's load latency hides
 // behind the dependent steps of the batches in front of it instead of stalling every lane of the wave.
 constexpr int kZcAhead = 2;
-template <class ColT> __device__ __forceinline__ void zc_load8(int (&v)[8], const ColT &yb, int q) {
+template <class ColT> __device__ __forceinline__ void zc_load8(int (&v)[8], const ColT &yb, int q, int rail) {
    #pragma unroll
-   for (int k = 0; k < 8; ++k) v[k] = yb[q + k]; }
+   for (int k = 0; k < 8; ++k) v[k] = zc_code(yb[q + k], rail); }
 struct ZcAhead { int v[kZcAhead][8]; };
-template <class ColT> __device__ __forceinline__ void zc_own_rows(ZcLane &me, const Zc32 z0, const ColT &yb, int j, int P, const ZcAhead *pre = nullptr) {
+template <class ColT> __device__ __forceinline__ void zc_own_rows(ZcLane &me, const Zc32 z0, const ColT &yb, int j, int P, int rail, const ZcAhead *pre = nullptr) {
    int cnt = 0;
    Zc32 z = z0;
    const int qend = (j + 1) * kZcSub;
@@ -1013,7 +1018,7 @@ template <class ColT> __device__ __forceinline__ void zc_own_rows(ZcLane &me, co
    if (pre) nx = *pre;
    else {
       #pragma unroll
-      for (int a = 0; a < kZcAhead; ++a) zc_load8(nx.v[a], yb, j * kZcSub + 8 * a); }
+      for (int a = 0; a < kZcAhead; ++a) zc_load8(nx.v[a], yb, j * kZcSub + 8 * a, rail); }
    #pragma nounroll
    for (int q = j * kZcSub; q < qend; q += 8) {
       int v8[8];
@@ -1023,7 +1028,7 @@ template <class ColT> __device__ __forceinline__ void zc_own_rows(ZcLane &me, co
       for (int a = 0; a + 1 < kZcAhead; ++a) {
          #pragma unroll
          for (int k = 0; k < 8; ++k) nx.v[a][k] = nx.v[a + 1][k]; }
-      zc_load8(nx.v[kZcAhead - 1], yb, min(q + 8 * kZcAhead, qend - 8));       // (behind the last batch: that batch again - no branch, no row outside the tile)
+      zc_load8(nx.v[kZcAhead - 1], yb, min(q + 8 * kZcAhead, qend - 8), rail);       // (behind the last batch: that batch again - no branch, no row outside the tile)
       #pragma unroll
       for (int k = 0; k < 8; ++k) {
          int cross;
@@ -1046,7 +1051,7 @@ template <class WT, bool kGlobal = false> __device__ __forceinline__ void zeros_
    const DevCfg *cfg = cx.cfg;
    const Tile &tl = cx.tile;
    const int ntrks = cfg->ntrks, nsub = tl.nrows / kZcSub;
-   const int P = cfg->zc_peak_i;
+   const int P = cfg->zc_peak_i, rail = zc_rail(cfg);
    // thread -> (sub-segment, track), the tracks of a sub-segment side by side: neighbouring lanes then read the 18 bytes of one row
    // (one or two cache lines per sub-segment and load, not one per lane); the lanes' records stay track-major (L)
    const int T = threadIdx.x, j = T / ntrks, trk = T - j * ntrks;
@@ -1066,12 +1071,12 @@ template <class WT, bool kGlobal = false> __device__ __forceinline__ void zeros_
       if (j == 0) {
          ZcState zs; zc_load(zs, walkers[trk]); z = zc_to32(zs, tl.row0);
          #pragma unroll
-         for (int a = 0; a < kZcAhead; ++a) zc_load8(nx.v[a], yb, 8 * a); }
+         for (int a = 0; a < kZcAhead; ++a) zc_load8(nx.v[a], yb, 8 * a, rail); }
       else {
          const int q0 = j * kZcSub - cfg->zc_warm;
-         Zc32 zw; zw.prev = yb[q0 - 1]; zw.top = 0; zw.bot = 0; zw.ttop = kZcNone; zw.tbot = kZcNone;
+         Zc32 zw; zw.prev = zc_code(yb[q0 - 1], rail); zw.top = 0; zw.bot = 0; zw.ttop = kZcNone; zw.tbot = kZcNone;
          #pragma unroll
-         for (int a = 0; a < kZcAhead; ++a) zc_load8(nx.v[a], yb, q0 + 8 * a);
+         for (int a = 0; a < kZcAhead; ++a) zc_load8(nx.v[a], yb, q0 + 8 * a, rail);
          #pragma nounroll
          for (int q = q0; q < j * kZcSub; q += 8) {                   // (the batches behind this one are in flight during its eight dependent steps; the ones read last are the first of the own rows)
             int v8[8];
@@ -1081,12 +1086,12 @@ template <class WT, bool kGlobal = false> __device__ __forceinline__ void zeros_
             for (int a = 0; a + 1 < kZcAhead; ++a) {
                #pragma unroll
                for (int k = 0; k < 8; ++k) nx.v[a][k] = nx.v[a + 1][k]; }
-            zc_load8(nx.v[kZcAhead - 1], yb, q + 8 * kZcAhead);
+            zc_load8(nx.v[kZcAhead - 1], yb, q + 8 * kZcAhead, rail);
             #pragma unroll
             for (int k = 0; k < 8; ++k) { int cross; (void)zc_step32(zw, v8[k], q + k, P, cross); } }
          z = zw; }
       me.start = z;
-      zc_own_rows(me, z, yb, j, P, &nx); }
+      zc_own_rows(me, z, yb, j, P, rail, &nx); }
    __syncthreads();
    if (dbgp) k1 = clock64();
    // Does every sub-segment start where its predecessor ended?  Where one does not, it alone is run again (its own 64 rows) from
@@ -1111,7 +1116,7 @@ template <class WT, bool kGlobal = false> __device__ __forceinline__ void zeros_
          const auto yb = zc_col<kGlobal>(tl, trk, cfg->skew[trk]);
          const Zc32 zp = lanes[L - 1].end;
          me.start = zp;
-         zc_own_rows(me, zp, yb, j, P); }
+         zc_own_rows(me, zp, yb, j, P, rail); }
       __syncthreads(); }
    if (dbgp) k2 = clock64();
    if (mine && ok[trk]) {                                            // events in row order; the walker moves to the tile's end
@@ -1120,7 +1125,7 @@ template <class WT, bool kGlobal = false> __device__ __forceinline__ void zeros_
       for (int k = 0; k < j; ++k) idx += (unsigned)lanes[L - j + k].count;
       for (int k = 0; k < me.count && k < kZcMaxEv; ++k) {
          const long long n = tl.row0 + (long long)(me.ev[k][0] & 0xffff);
-         const int v = (int)(short)(me.ev[k][0] >> 16);
+         const int v = zc_code((int)(short)(me.ev[k][0] >> 16), rail);
          zc_event(cx, trk, idx + k, n, v, (me.ev[k][1] >> 31) != 0, n - (long long)(me.ev[k][1] & 0x7fffffffu)); } }
    __syncthreads();
    if (T < ntrks && ok[T]) {
@@ -1219,15 +1224,15 @@ __device__ __forceinline__ void walk_diffzeros(Walker &w, Ctx &cx, int trk, long
    const long long tile_end = tl.row0 + tl.nrows;
    if (limit > tile_end) limit = tile_end;
    const float mv = cfg->maxvolts;
-   const int d = cfg->skew[trk];
+   const int d = cfg->skew[trk], rail = zc_rail(cfg);
    const int spb = cfg->samples_per_bit;
    long long n = w.next;
    if (n <= w.start) n = w.start + 1;                              // row `start` only seeds the track (src/decoder.c:855-861)
    for (; n < limit; ++n) {
       // what the detector sees at row n: the differentiated sample of row src (deskew FIFO, src/decoder.c:825-828)
       const long long src = (n - tl.reset < d) ? n : n - d;
-      const float vraw = volt(tl.xi(trk, src), mv);
-      const float vprev = src == tl.reset ? 0.0f : volt(tl.xi(trk, src - 1), mv);   // v_last_raw = 0 at the restart (src/decoder.c:437)
+      const float vraw = volt(zc_code(tl.xi(trk, src), rail), mv);
+      const float vprev = src == tl.reset ? 0.0f : volt(zc_code(tl.xi(trk, src - 1), rail), mv);   // v_last_raw = 0 at the restart (src/decoder.c:437)
       float delta = vraw - vprev;
       if (delta < 0.05f && delta > -0.05f) delta = 0;
       const float v = delta * 0.4f * spb;

@@ -6,6 +6,7 @@ writes such shapes over peaks of a clean NRZI tape - every sample of the window 
 "a hair below the peak", "a little below", "well below" - and checks every event against the oracle.
 
   python tools/fuzz_shapes.py [--gpu] [--e2e] [seed0 [ntapes [kind]]]     (test infrastructure: the oracle through tests/parity_util; without --gpu the kernels run on tests/cpu_emul)
+  python tools/fuzz_shapes.py [--gpu] --zeros | --diffz [seed0 [ntapes]]   (-zeros / -zeros -differentiate: tests/zeros_shapes.py's tapes end to end against the oracle)
 """
 import os
 import sys
@@ -34,6 +35,8 @@ def main():
     else:
         from emul_util import emul_frontend
         make = emul_frontend
+    if "--zeros" in sys.argv or "--diffz" in sys.argv:
+        return zeros_main(make, gpu, seed0, ntapes, diff="--diffz" in sys.argv)
     bad = 0
     for seed in range(seed0, seed0 + ntapes):
         d = draw(seed)
@@ -68,6 +71,29 @@ def main():
             if msgs:
                 bad += 1
                 print("\n".join(msgs[:6]), flush=True)
+    print("FAILURES", bad)
+    return 1 if bad else 0
+
+
+def zeros_main(make, gpu, seed0, ntapes, diff):
+    import zeros_shapes as zs
+    from readtape_amd import frontend
+
+    def bursts(hdr, rows):
+        return make(frontend.FrontEndConfig.from_header(hdr, find_zeros=True)).scan(rows).fetch(events=False).bursts
+    bad = 0
+    for seed in range(seed0, seed0 + ntapes):
+        hdr, rows0, rows, sites, opts = zs.shaped(seed, bursts, diff=diff)
+        if seed % 4 == 3 and not diff:
+            opts = opts + ["-invert"]                          # (k_decode's zero-crossing mode)
+        with tempfile.TemporaryDirectory() as wd:
+            msgs, b = zs.e2e(hdr, rows, opts, wd, None if gpu else make)
+        cov = zs.coverage(sites, hdr, rows.shape[0], bursts(hdr, rows))
+        print(f"{'ok' if not msgs else 'FAIL'} seed {seed} {zs.draw(seed)} {' '.join(opts)} sites {len(sites)} transitions {b.size} "
+              f"seams {sum(cov.get(c, 0) for c in zs.SEAMS)}", flush=True)
+        if msgs:
+            bad += 1
+            print("\n".join(str(x) for x in msgs[:6]), flush=True)
     print("FAILURES", bad)
     return 1 if bad else 0
 
