@@ -245,6 +245,73 @@ int rtfe_ww_scan(rtfe_handle *h, const int16_t *d_rows, int64_t nrows, int64_t r
                  const rtfe_ww_track *d_state_in, rtfe_ww_track *d_state_out, uint32_t *d_counts, rtfe_event *d_events, int64_t event_capacity,
                  uint32_t *d_flags, void *stream);
 
+/* ---- Whirlwind with -zeros and / or -differentiate: the other three detectors, same contract ----
+ * The reference picks its detector by option for every mode (src/decoder.c:863-866) and differentiates in readblock whatever the mode
+ * (src/readtape.c:1383-1388,1422).  A handle made for RTFE_WW with find_zeros and / or differentiate runs, through rtfe_ww_detector_scan,
+ *   RTFE_WW_ZEROS      find_zeros                   lookfor_zerocrossing                  src/decoder.c:617-649   on the samples
+ *   RTFE_WW_DIFFZEROS  find_zeros + differentiate   lookfor_differentiated_zerocrossing   src/decoder.c:654-683   on differentiate()'s output
+ *   RTFE_WW_DIFFPEAKS  differentiate                lookfor_peak / refine_peak            src/decoder.c:751-810   on differentiate()'s output
+ * (RTFE_WW_PEAKS: neither option - rtfe_ww_scan and rtfe_ww_track above, unchanged.)  Rows, seed_row0, per-track event lists and the state
+ * in / state out are as for rtfe_ww_scan; on its seed row and the rows in front of it a track runs NO detector (the `break` of
+ * src/decoder.c:861), but differentiate() has run on them (v_last_raw follows every row).  Nothing restarts between blocks, so everything
+ * the detectors remember is in the state, rows as ABSOLUTE rows of the tape: a crossing armed in one chunk or attempt - or, after the
+ * -deskew rewind, at a row that lies AHEAD - is confirmed correctly in a later one.
+ * The ABI version did not move for these entry points: they are additions, nothing that existed changed its layout or its behaviour
+ * (rtfe_event, rtfe_ww_track, rtfe_ww_scan and rtfe_ww_initial_state are what they were), and rtfe_create now accepts what it refused. */
+enum { RTFE_WW_PEAKS = 0, RTFE_WW_ZEROS = 1, RTFE_WW_DIFFZEROS = 2, RTFE_WW_DIFFPEAKS = 3 };
+
+typedef struct rtfe_ww_dtrack {
+   int32_t kind;                    /* RTFE_WW_ZEROS / _DIFFZEROS / _DIFFPEAKS: a blob only meets a handle of its own kind (RTFE_F_STATE_KIND) */
+   int32_t delay;                   /* -deskew: this track's delay in samples (0..50), as rtfe_ww_track::delay; differentiate() runs in front of the delay line */
+   int32_t v_last_raw;              /* differentiate(): the code (after -invert, so -32768 .. 32768) of the last row read, src/readtape.c:1387 */
+   int32_t v_raw_row0;              /* ... and what row 0 of the tape is differentiated against: 0, or after the -deskew rewind the last row the pre-pass read */
+   /* the zero-crossing detectors */
+   int32_t z_prev, z_top, z_bot;    /* RTFE_WW_ZEROS: v_prev, v_top, v_bot as codes */
+   int32_t up_pending, dn_pending;  /* zerocross_up_pending / zerocross_dn_pending */
+   float   zf_top, zf_bot;          /* RTFE_WW_DIFFZEROS: v_top, v_bot in volts (differentiated) */
+   int32_t have_zero;               /* RTFE_WW_DIFFZEROS: t_firstzero != 0 */
+   int64_t row_top, row_bot;        /* RTFE_WW_ZEROS: t_top / t_bot of a pending crossing, as absolute rows */
+   int64_t row_firstzero, row_lastzero;   /* RTFE_WW_DIFFZEROS: t_firstzero / t_lastzero as absolute rows */
+   /* RTFE_WW_DIFFPEAKS: the window (differentiated volts; a re-seeded window keeps stale slots) and the AGC, as rtfe_ww_track */
+   int32_t left, right, countdown, peakcount, heightndx, pad;
+   float   maxv, minv;
+   float   agc_gain, v_avg_height, v_lasttop, v_lastbot, v_top, v_bot;
+   float   heights[10];
+   float   ring[64];
+} rtfe_ww_dtrack;                    /* 432 bytes */
+
+/* One call of ww_top / ww_bot: an rtfe_event (sample relative to first_row; flags bit 0 = bottom; RTFE_WW_DIFFPEAKS: every field as
+ * rtfe_ww_scan fills it, v_peak a differentiated value) and behind it what the 16 bytes cannot hold:
+ *   RTFE_WW_ZEROS      back_first = rows from the sign change to the confirming row; the slope gate of src/decoder.c:629,643 is the host's
+ *   RTFE_WW_DIFFZEROS  has_zero != 0: back_first / back_last = rows from the first / last exact zero of the run to the confirming row, exact for
+ *                      any distance (the run can span an inter-block gap); has_zero = 0: the crossing lies half a sample before the row.
+ *                      v_other = the OPPOSITE excursion as the reference still holds it at the callback (it zeroes it only afterwards,
+ *                      src/decoder.c:663-667, 676-680): the -deskew pre-pass reads v_top - v_bot (src/decoder.c:484-489)
+ * The offsets are signed: after the -deskew rewind a pending row can lie ahead of the row that confirms it. */
+typedef struct rtfe_ww_event {
+   rtfe_event ev;
+   float      v_other;
+   uint32_t   has_zero;
+   int64_t    back_first, back_last;
+} rtfe_ww_event;                     /* 40 bytes */
+
+#define RTFE_F_STATE_KIND 256        /* rtfe_ww_detector_scan: a track's state blob is not of the handle's kind; nothing was scanned */
+
+/* Which detector the handle runs (RTFE_WW_*; -1: not a Whirlwind handle), and the bytes of ONE track's state for it (224 for RTFE_WW_PEAKS).
+ * Replaces: the dispatch of src/decoder.c:863-866. */
+int    rtfe_ww_state_kind(const rtfe_handle *h);
+size_t rtfe_ww_state_bytes(const rtfe_handle *h);
+/* The state a tape starts from (host memory, ntrks tracks of rtfe_ww_state_bytes each; state_bytes = the size of the whole buffer, checked).
+ * Replaces: init_trackstate, src/decoder.c:425-455. */
+int rtfe_ww_detector_initial_state(const rtfe_handle *h, void *tracks, size_t state_bytes);
+/* The scan; state_bytes = the size of each of the two state buffers (ntrks rtfe_ww_dtrack).  Errors (rtfe_last_error): a handle of kind
+ * RTFE_WW_PEAKS, a state buffer of another size.  A blob of another kind: RTFE_F_STATE_KIND in *d_flags, no events, state handed back as it came.
+ * Replaces: lookfor_zerocrossing, lookfor_differentiated_zerocrossing and lookfor_peak behind differentiate() (src/decoder.c:617-683, 751-810;
+ * src/readtape.c:1383-1388) for mode WW, at the seam of src/decoder.c:586,604. */
+int rtfe_ww_detector_scan(rtfe_handle *h, const int16_t *d_rows, int64_t nrows, int64_t row_base, int64_t first_row, int64_t nscan, int64_t seed_row0,
+                          const void *d_state_in, void *d_state_out, size_t state_bytes, uint32_t *d_counts, rtfe_ww_event *d_events,
+                          int64_t event_capacity, uint32_t *d_flags, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -54,21 +54,26 @@ static int pred_gcr(const struct rt_dec *d, const struct rt_trk *t, double timen
 
 /* ---- the event source of one attempt: per-track lists of one (burst, parmset) ---- */
 struct evsrc {
-   const rtfe_event *list[RT_MAXTRKS];
+   const unsigned char *list[RT_MAXTRKS];
+   size_t stride;           /* bytes from one record of a list to the next: sizeof(rtfe_event), or sizeof(rtfe_ww_event) (an rtfe_event in front) */
    uint32_t n[RT_MAXTRKS], at[RT_MAXTRKS];
    int64_t nr[RT_MAXTRKS];  /* absolute row of each track's next event, INT64_MAX when its list is used up (evsrc_sync keeps it) */
    int64_t reset;           /* absolute row of sample 0 */
    int64_t end;             /* rows >= end are not covered by this source */
 };
 
+static inline const rtfe_event *evsrc_ev(const struct evsrc *s, int t, uint32_t i) {
+   return (const rtfe_event *)(s->list[t] + (size_t)i * s->stride); }
+
 static inline void evsrc_sync(struct evsrc *s, int t) {
-   s->nr[t] = s->at[t] < s->n[t] ? s->reset + (int64_t)s->list[t][s->at[t]].sample : INT64_MAX; }
+   s->nr[t] = s->at[t] < s->n[t] ? s->reset + (int64_t)evsrc_ev(s, t, s->at[t])->sample : INT64_MAX; }
 
 static void evsrc_from_burst(struct evsrc *s, const struct rt_replay *rp, int64_t b, int parmset) {
    const rtfe_burst *B = &rp->bursts[b];
    if (rp->find_zeros) parmset = 0;           /* the zero-crossing front end does not depend on the parameter set */
+   s->stride = sizeof(rtfe_event);
    for (int t = 0; t < rp->ntrks; ++t) {
-      s->list[t] = rp->events + B->event_base + (uint64_t)(parmset * rp->ntrks + t) * B->event_cap;
+      s->list[t] = (const unsigned char *)(rp->events + B->event_base + (uint64_t)(parmset * rp->ntrks + t) * B->event_cap);
       s->n[t] = rp->counts[((size_t)b * rp->nparm + parmset) * rp->ntrks + t];
       s->at[t] = 0; }
    s->reset = B->reset_sample - rp->row_base;
@@ -83,7 +88,7 @@ static inline int64_t evsrc_next_row(const struct evsrc *s, int ntrks) {
 static void evsrc_skip_before(struct evsrc *s, int ntrks, int64_t row) {
    for (int t = 0; t < ntrks; ++t)
       if (s->nr[t] < row) {
-         while (s->at[t] < s->n[t] && s->reset + s->list[t][s->at[t]].sample < row) ++s->at[t];
+         while (s->at[t] < s->n[t] && s->reset + evsrc_ev(s, t, s->at[t])->sample < row) ++s->at[t];
          evsrc_sync(s, t); } }
 
 static int64_t find_burst(const struct rt_replay *rp, int64_t s0) {
@@ -114,6 +119,28 @@ void rt_replay_restore_pos(void *ctx) {
 static void deliver(struct rt_replay *rp, const struct evsrc *s, int trk, const rtfe_event *e, int W) {
    struct rt_dec *d = rp->d;
    struct rt_trk *t = &d->trk[trk];
+   if (s->stride == sizeof(rtfe_ww_event) && rp->find_zeros) {
+      /* Whirlwind (rtfe_ww_detector_scan): the same two deliveries from the wide record - offsets of any length and of either sign (nothing
+       * restarts between blocks, and the -deskew rewind leaves pending rows AHEAD of the rows that confirm them), and for the differentiated
+       * detector the opposite excursion as the reference holds it at the callback (src/decoder.c:663-667, 676-680: it zeroes it afterwards),
+       * which the -deskew pre-pass reads (rt_decode_ww.c: v_top - v_bot per pulse end) */
+      const rtfe_ww_event *we = (const rtfe_ww_event *)e;
+      const int64_t row = s->reset + (int64_t)e->sample;
+      if (d->opt.do_differentiate) {
+         const double tz = we->has_zero ? (time_of_row(rp, row - we->back_first) + time_of_row(rp, row - we->back_last)) / 2
+                                        : d->timenow - d->sample_deltat / 2;
+         if (e->flags & 1) { t->v_bot = e->v_peak; t->v_top = we->v_other; t->t_bot = tz; rt_down_transition(d, t); }
+         else { t->v_top = e->v_peak; t->v_bot = we->v_other; t->t_top = tz; rt_up_transition(d, t); }
+         ++rp->events_delivered;
+         return; }
+      const double t_cross = time_of_row(rp, row - we->back_first);
+      if (e->flags & 1) {
+         t->v_bot = e->v_peak; t->t_bot = t_cross; t->v_top = 0;
+         if (d->timenow - t->t_bot <= t->clkavg.t_bitspaceavg * 1.5f) { rt_down_transition(d, t); ++rp->events_delivered; } }
+      else {
+         t->v_top = e->v_peak; t->t_top = t_cross; t->v_bot = 0;
+         if (d->timenow - t->t_top <= t->clkavg.t_bitspaceavg * 1.5f) { rt_up_transition(d, t); ++rp->events_delivered; } }
+      return; }
    if (rp->find_zeros && d->opt.do_differentiate) {
       /* differentiated signal (src/decoder.c:657-663, 670-676): the crossing is the centre of the run of exact
        * zeros if there was one, else half a sample before the confirming row; no slope gate */
@@ -208,7 +235,8 @@ restart:
       const int64_t ex_end = s0 + exact_len < nrows ? s0 + exact_len : nrows;
       if (rp->exact(rp->exact_user, s0, ex_end, rp->find_zeros ? 0 : parmset, &eb, cnt, &exact_events, &cap) != 0) {
          ++rp->device_failures; d->results[parmset].blktype = RT_BS_ABORTED; rt_finish_attempt(d); return 0; }
-      for (int t = 0; t < ntrks; ++t) { src.list[t] = exact_events + (uint64_t)t * cap; src.n[t] = cnt[t]; src.at[t] = 0; }
+      src.stride = sizeof(rtfe_event);
+      for (int t = 0; t < ntrks; ++t) { src.list[t] = (const unsigned char *)(exact_events + (uint64_t)t * cap); src.n[t] = cnt[t]; src.at[t] = 0; }
       src.reset = s0; src.end = ex_end;
       for (int t = 0; t < ntrks; ++t) evsrc_sync(&src, t);
       using_exact = 1; ++rp->exact_scans; }
@@ -294,13 +322,13 @@ restart:
             if (t >= ntrk_started) ntrk_started = t + 1;
             break; }
          while (src.nr[t] == row) {
-            if (src.list[t][src.at[t]].flags & RTFE_EV_FATAL) {    /* "AGC gain bad in lookfor_peak" (src/decoder.c:782): the reference exits here */
+            if (evsrc_ev(&src, t, src.at[t])->flags & RTFE_EV_FATAL) {    /* "AGC gain bad in lookfor_peak" (src/decoder.c:782): the reference exits here */
                rp->reference_fatal = 1; d->fatal = 1; rp->fatal_row = row; rp->fatal_trk = t;
                d->results[parmset].blktype = RT_BS_ABORTED;
                if (exact_events && rp->exact_free) rp->exact_free(rp->exact_user, exact_events);
                rt_finish_attempt(d);
                return 0; }
-            deliver(rp, &src, t, &src.list[t][src.at[t]], W);
+            deliver(rp, &src, t, evsrc_ev(&src, t, src.at[t]), W);
             if (d->fatal) {                                      /* the decoder's callback met one of the reference's asserts (a learned peak height that is not positive): the run ends inside it */
                rp->reference_fatal = 1; rp->fatal_row = row; rp->fatal_trk = t;
                d->results[parmset].blktype = RT_BS_ABORTED;
@@ -522,7 +550,7 @@ static int ww_readblock(void *ctx, int retry) {
    struct rt_replay *rp = (struct rt_replay *)ctx;
    struct rt_dec *d = rp->d;
    const int ntrks = rp->ntrks, W = rp->W[0];
-   const size_t sbytes = (size_t)ntrks * sizeof(rtfe_ww_track);
+   const size_t sbytes = (size_t)ntrks * rp->ww_track_bytes;
    const int64_t s0 = rp->pos, nrows = rp->nrows, L = rp->ww_chunk_rows;
    int endfile = 0;
    (void)retry;
@@ -537,7 +565,8 @@ static int ww_readblock(void *ctx, int retry) {
       if (!have_chunk) {                                      /* the events of rows [chunk_first, chunk_first + L) */
          if (rp->ww_scan(rp->ww_user, chunk_first, L, s0, rp->ww_chunk_state, rp->ww_chunk_end, rp->ww_counts, rp->ww_events, rp->ww_cap) != 0) {
             ++rp->device_failures; d->results[d->parmset].blktype = RT_BS_ABORTED; rt_finish_attempt(d); return 0; }
-         for (int t = 0; t < ntrks; ++t) { src.list[t] = rp->ww_events + (size_t)t * rp->ww_cap; src.n[t] = rp->ww_counts[t]; src.at[t] = 0; }
+         src.stride = rp->ww_event_bytes;
+         for (int t = 0; t < ntrks; ++t) { src.list[t] = (const unsigned char *)rp->ww_events + (size_t)t * rp->ww_cap * src.stride; src.n[t] = rp->ww_counts[t]; src.at[t] = 0; }
          src.reset = chunk_first; src.end = chunk_first + L;
          for (int t = 0; t < ntrks; ++t) evsrc_sync(&src, t);
          ++rp->exact_scans;
@@ -559,6 +588,9 @@ static int ww_readblock(void *ctx, int retry) {
          d->timenow = time_of_row(rp, nrows - 1);
          rp->pos = nrows;
          endfile = 1;
+         /* the zero-crossing state and the differentiator's last sample survive the -deskew rewind: a pre-pass that read to the end of the data
+          * hands the decode the state behind the LAST row (the scan stops at the end of the data; src.end >= nrows here) */
+         if (rp->ww_event_bytes == sizeof(rtfe_ww_event)) memcpy(rp->ww_state, rp->ww_chunk_end, sbytes);
          break; }
       row = next;
       rp->cur_row = row;
@@ -570,12 +602,12 @@ static int ww_readblock(void *ctx, int retry) {
             tk->t_lastpeak = d->timenow;
             break; }
          while (src.nr[t] == row) {
-            if (src.list[t][src.at[t]].flags & RTFE_EV_FATAL) {
+            if (evsrc_ev(&src, t, src.at[t])->flags & RTFE_EV_FATAL) {
                rp->reference_fatal = 1; d->fatal = 1; rp->fatal_row = row; rp->fatal_trk = t;
                d->results[d->parmset].blktype = RT_BS_ABORTED;
                rt_finish_attempt(d);
                return 0; }
-            deliver(rp, &src, t, &src.list[t][src.at[t]], W);
+            deliver(rp, &src, t, evsrc_ev(&src, t, src.at[t]), W);
             ++src.at[t]; evsrc_sync(&src, t); } }
       evsrc_skip_before(&src, ntrks, row + 1);
       if (rt_ww_end_due(d)) rt_ww_end_of_block(d);             /* src/decoder.c:892-894 */
@@ -593,7 +625,34 @@ int rt_replay_run_ww(const struct rt_options *opt, const struct rt_parms *parmse
                   int64_t tdelta_ns, int64_t tstart_ns, int64_t nrows, int W0, rt_ww_scan_fn scan, void *user, const void *initial_state, int64_t chunk_rows,
                   const char *tap_path, const char *out_base, const char *in_name, const char *log_path, const char *evt_path, struct rt_replay_stats *stats,
                   int deskew, int *delays_out) {
+   return rt_replay_run_ww_detector(opt, parmsets, tdelta_ns, tstart_ns, nrows, W0, scan, user, initial_state, sizeof(rtfe_ww_track), chunk_rows,
+                                    tap_path, out_base, in_name, log_path, evt_path, stats, deskew, delays_out); }
+
+/* what the -deskew restart does to the device detector's state (src/readtape.c:1676-1716): init_trackpeak_state (src/decoder.c:413-423) clears the
+ * window's indices, extremes and countdown and the delay lines - nothing else: the rings, the AGC, the zero detectors' extremes, pending flags and
+ * rows and the differentiator's last sample survive the rewind, so the second pass differentiates its first row against the last row the pre-pass
+ * read.  The two state kinds of include/rt_frontend.h, told apart by the options that made them. */
+static void ww_rewind_state(unsigned char *state, int wide, int ntrks, const struct rt_dec *d, const int *delays) {
+   for (int t = 0; t < ntrks; ++t) {
+      if (wide) {
+         rtfe_ww_dtrack *st = (rtfe_ww_dtrack *)state + t;
+         st->left = st->right = st->countdown = 0; st->maxv = st->minv = 0;
+         st->v_avg_height = d->trk[t].v_avg_height;
+         st->delay = delays[t];
+         st->v_raw_row0 = st->v_last_raw; }
+      else {
+         rtfe_ww_track *st = (rtfe_ww_track *)state + t;
+         st->left = st->right = st->maxv = st->minv = st->countdown = 0;
+         st->v_avg_height = d->trk[t].v_avg_height;
+         st->delay = delays[t]; } } }
+
+int rt_replay_run_ww_detector(const struct rt_options *opt, const struct rt_parms *parmsets,
+                  int64_t tdelta_ns, int64_t tstart_ns, int64_t nrows, int W0, rt_ww_scan_fn scan, void *user, const void *initial_state, size_t track_bytes,
+                  int64_t chunk_rows, const char *tap_path, const char *out_base, const char *in_name, const char *log_path, const char *evt_path,
+                  struct rt_replay_stats *stats, int deskew, int *delays_out) {
    const float sample_deltat = (float)tdelta_ns / 1e9f;
+   const int wide = opt->find_zeros || opt->do_differentiate;    /* rtfe_ww_detector_scan: rtfe_ww_dtrack states, rtfe_ww_event records */
+   if (track_bytes != (wide ? sizeof(rtfe_ww_dtrack) : sizeof(rtfe_ww_track))) return -4;      /* a state of another detector */
    struct rt_options o = *opt;
    o.multiple_tries = 0;                                       /* "not implemented yet for Whirlwind" (src/readtape.c:1987) */
    struct rt_dec *d = rt_dec_new(&o, sample_deltat, tdelta_ns);
@@ -607,12 +666,14 @@ int rt_replay_run_ww(const struct rt_options *opt, const struct rt_parms *parmse
    rp.d = d; rp.ntrks = o.ntrks; rp.nparm = 1; rp.W[0] = W0;
    rp.nrows = nrows; rp.tstart_ns = tstart_ns; rp.tdelta_ns = tdelta_ns; rp.stop_row = INT64_MAX;
    rp.ww_scan = scan; rp.ww_user = user;
+   rp.find_zeros = o.find_zeros;
+   rp.ww_track_bytes = track_bytes; rp.ww_event_bytes = wide ? sizeof(rtfe_ww_event) : sizeof(rtfe_event);
    rp.ww_chunk_rows = chunk_rows > 64 ? chunk_rows : 64;
    rp.ww_cap = (uint32_t)rp.ww_chunk_rows;                     /* (no more events than rows) */
-   const size_t sbytes = (size_t)o.ntrks * sizeof(rtfe_ww_track);
+   const size_t sbytes = (size_t)o.ntrks * track_bytes;
    rp.ww_state = (unsigned char *)malloc(3 * sbytes); rp.ww_chunk_state = rp.ww_state + sbytes; rp.ww_chunk_end = rp.ww_state + 2 * sbytes;
    memcpy(rp.ww_state, initial_state, sbytes);
-   rp.ww_events = (rtfe_event *)malloc((size_t)o.ntrks * rp.ww_cap * sizeof(rtfe_event));
+   rp.ww_events = (rtfe_event *)malloc((size_t)o.ntrks * rp.ww_cap * rp.ww_event_bytes);
    rp.ww_counts = (uint32_t *)calloc((size_t)o.ntrks, sizeof(uint32_t));
    if (evt_path) {
       rp.evtf = fopen(evt_path, "wb");
@@ -630,11 +691,7 @@ int rt_replay_run_ww(const struct rt_options *opt, const struct rt_parms *parmse
       rt_replay_restore_pos(&rp);
       if (nblks < 0 || rp.device_failures || rp.reference_fatal) prepass_failed = 1;
       else {
-         rtfe_ww_track *st = (rtfe_ww_track *)rp.ww_state;
-         for (int t = 0; t < o.ntrks; ++t) {
-            st[t].left = st[t].right = st[t].maxv = st[t].minv = st[t].countdown = 0;
-            st[t].v_avg_height = d->trk[t].v_avg_height;
-            st[t].delay = delays[t]; }
+         ww_rewind_state(rp.ww_state, wide, o.ntrks, d, delays);
          if (delays_out) memcpy(delays_out, delays, sizeof(int) * (size_t)o.ntrks); } }
    const int ok = prepass_failed ? 0 : rt_process_blocks(d, &rd, 0x7fffffff);
    if (in_name) rt_write_summary(d, in_name, difftime(time(NULL), (time_t)wall0));

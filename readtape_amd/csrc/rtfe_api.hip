@@ -179,8 +179,8 @@ static int create_impl(const rtfe_config *c, rtfe_handle **out, int tile_overrid
    if (c->ntrks < 1 || c->ntrks > RTFE_MAXTRKS) return fail(-2, "ntrks %d out of range", c->ntrks);
    if (c->mode != RTFE_NRZI && c->mode != RTFE_PE && c->mode != RTFE_GCR && c->mode != RTFE_WW)
       return fail(-3, "mode %d not known", c->mode);
-   if (c->mode == RTFE_WW && (c->nparmsets != 1 || c->find_zeros || c->differentiate))
-      return fail(-3, "Whirlwind: one parameter set, peak detection on the undifferentiated signal (rtfe_ww_scan)");
+   if (c->mode == RTFE_WW && c->nparmsets != 1)
+      return fail(-3, "Whirlwind: one parameter set (rtfe_ww_scan; with -zeros / -differentiate rtfe_ww_detector_scan)");
    if (c->nparmsets < 1 || c->nparmsets > RTFE_MAXPARMSETS) return fail(-5, "nparmsets %d out of range", c->nparmsets);
    if (c->nparmsets * c->ntrks > kDecodeThreads) return fail(-6, "nparmsets*ntrks > %d", kDecodeThreads);
    if (!(c->bpi >= 0) || !(c->ips > 0) || c->tdelta_ns <= 0 || !(c->maxvolts > 0)) return fail(-7, "ips, tdelta_ns and maxvolts must be positive, bpi >= 0");
@@ -1000,9 +1000,50 @@ extern "C" int rtfe_ww_scan(rtfe_handle *h, const int16_t *d_rows, int64_t nrows
                             uint32_t *d_flags, void *stream) {
    if (!h || !d_rows || !d_state_in || !d_state_out || !d_counts || !d_events || !d_flags) return fail(-1, "null argument");
    if (h->dev.mode != RTFE_WW) return fail(-40, "rtfe_ww_scan: the handle was not made for mode RTFE_WW");
-   if (h->dev.find_zeros || h->dev.differentiate || h->dev.maxskew > 0 || h->dev.nparm != 1) return fail(-41, "rtfe_ww_scan: peak detection, one parameter set, deskew delays in the state (not in the configuration)");
+   if (h->dev.find_zeros || h->dev.differentiate) return fail(-41, "rtfe_ww_scan: peak detection on the undifferentiated signal; this handle was made with -zeros / -differentiate (rtfe_ww_detector_scan)");
+   if (h->dev.maxskew > 0 || h->dev.nparm != 1) return fail(-41, "rtfe_ww_scan: peak detection, one parameter set, deskew delays in the state (not in the configuration)");
    if (h->dev.parm[0].W > kWwRing) return fail(-42, "window wider than the state's ring");
    if (first_row < 0 || nscan <= 0 || first_row >= nrows || seed_row0 > first_row || event_capacity < 1) return fail(-43, "bad row range");
    hipLaunchKernelGGL(k_ww, dim3(1), dim3(64), 0, (hipStream_t)stream, (const DevCfg *)h->d_dev, d_rows, (long long)nrows, (long long)row_base,
                       (long long)first_row, (long long)nscan, (long long)seed_row0, d_state_in, d_state_out, d_counts, d_events, (long long)event_capacity, d_flags);
    return launch_check("rtfe_ww_scan"); }
+
+// ---- Whirlwind with -zeros and / or -differentiate (include/rt_frontend.h) ----
+static int ww_kind(const rtfe_handle *h) {
+   if (!h || h->dev.mode != RTFE_WW) return -1;
+   return h->dev.find_zeros ? (h->dev.differentiate ? RTFE_WW_DIFFZEROS : RTFE_WW_ZEROS) : (h->dev.differentiate ? RTFE_WW_DIFFPEAKS : RTFE_WW_PEAKS); }
+
+extern "C" int rtfe_ww_state_kind(const rtfe_handle *h) { return ww_kind(h); }
+
+extern "C" size_t rtfe_ww_state_bytes(const rtfe_handle *h) {
+   const int k = ww_kind(h);
+   return k < 0 ? 0 : (k == RTFE_WW_PEAKS ? sizeof(rtfe_ww_track) : sizeof(rtfe_ww_dtrack)); }
+
+extern "C" int rtfe_ww_detector_initial_state(const rtfe_handle *h, void *tracks, size_t state_bytes) {
+   if (!h || !tracks) return fail(-1, "null argument");
+   const int k = ww_kind(h);
+   if (k < 0) return fail(-40, "rtfe_ww_detector_initial_state: the handle was not made for mode RTFE_WW");
+   const size_t want = rtfe_ww_state_bytes(h) * (size_t)h->dev.ntrks;
+   if (state_bytes != want) return fail(-45, "rtfe_ww_detector_initial_state: a state of %zu bytes, this handle's is %zu (%d tracks of %zu)", state_bytes, want, h->dev.ntrks, rtfe_ww_state_bytes(h));
+   if (k == RTFE_WW_PEAKS) { rtfe_ww_initial_state((rtfe_ww_track *)tracks, h->dev.ntrks); return 0; }
+   rtfe_ww_dtrack *st = (rtfe_ww_dtrack *)tracks;
+   memset(st, 0, want);                                               // src/decoder.c:437: everything but what follows
+   for (int t = 0; t < h->dev.ntrks; ++t) { st[t].kind = k; st[t].agc_gain = 1.0f; st[t].v_avg_height = 4.0f; }
+   return 0; }
+
+extern "C" int rtfe_ww_detector_scan(rtfe_handle *h, const int16_t *d_rows, int64_t nrows, int64_t row_base, int64_t first_row, int64_t nscan, int64_t seed_row0,
+                                     const void *d_state_in, void *d_state_out, size_t state_bytes, uint32_t *d_counts, rtfe_ww_event *d_events,
+                                     int64_t event_capacity, uint32_t *d_flags, void *stream) {
+   if (!h || !d_rows || !d_state_in || !d_state_out || !d_counts || !d_events || !d_flags) return fail(-1, "null argument");
+   const int k = ww_kind(h);
+   if (k < 0) return fail(-40, "rtfe_ww_detector_scan: the handle was not made for mode RTFE_WW");
+   if (k == RTFE_WW_PEAKS) return fail(-41, "rtfe_ww_detector_scan: this handle detects peaks on the undifferentiated signal (rtfe_ww_scan, rtfe_ww_track)");
+   if (h->dev.maxskew > 0 || h->dev.nparm != 1) return fail(-41, "rtfe_ww_detector_scan: one parameter set, deskew delays in the state (not in the configuration)");
+   const size_t want = sizeof(rtfe_ww_dtrack) * (size_t)h->dev.ntrks;
+   if (state_bytes != want) return fail(-45, "rtfe_ww_detector_scan: a state of %zu bytes, this handle's is %zu (%d tracks of %zu: rtfe_ww_dtrack)", state_bytes, want, h->dev.ntrks, sizeof(rtfe_ww_dtrack));
+   if (k == RTFE_WW_DIFFPEAKS && h->dev.parm[0].W > kWwRing) return fail(-42, "window wider than the state's ring");
+   if (first_row < 0 || nscan <= 0 || first_row >= nrows || seed_row0 > first_row || event_capacity < 1) return fail(-43, "bad row range");
+   hipLaunchKernelGGL(k_ww_det, dim3(1), dim3(64), 0, (hipStream_t)stream, (const DevCfg *)h->d_dev, d_rows, (long long)nrows, (long long)row_base,
+                      (long long)first_row, (long long)nscan, (long long)seed_row0, k, (const rtfe_ww_dtrack *)d_state_in, (rtfe_ww_dtrack *)d_state_out,
+                      d_counts, d_events, (long long)event_capacity, d_flags);
+   return launch_check("rtfe_ww_detector_scan"); }

@@ -29,6 +29,11 @@ BURST_DTYPE = np.dtype([("zone_first", "<i8"), ("zone_end", "<i8"), ("reset_samp
                         ("end_sample", "<i8"), ("event_base", "<u8"), ("event_cap", "<u4"), ("flags", "<u4")])
 PLAN_DTYPE = np.dtype([("event_base", "<u8"), ("event_cap", "<u4"), ("reserved", "<u4")])      # rtfe_pack_entry
 assert EVENT_DTYPE.itemsize == 16 and BURST_DTYPE.itemsize == 56 and PLAN_DTYPE.itemsize == 16
+# Whirlwind with -zeros / -differentiate (rtfe_ww_detector_scan): an rtfe_event and what it cannot hold (include/rt_frontend.h: rtfe_ww_event)
+WW_EVENT_DTYPE = np.dtype([("ev", EVENT_DTYPE), ("v_other", "<f4"), ("has_zero", "<u4"), ("back_first", "<i8"), ("back_last", "<i8")])
+assert WW_EVENT_DTYPE.itemsize == 40
+WW_PEAKS, WW_ZEROS, WW_DIFFZEROS, WW_DIFFPEAKS = 0, 1, 2, 3
+F_STATE_KIND = 256
 
 
 class _Parmset(C.Structure):
@@ -239,6 +244,11 @@ def _load_library(path=None):
     lib.rtfe_ww_initial_state.argtypes = [C.c_void_p, C.c_int]
     lib.rtfe_ww_scan.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    lib.rtfe_ww_state_kind.argtypes = [C.c_void_p]
+    lib.rtfe_ww_state_bytes.argtypes = [C.c_void_p]; lib.rtfe_ww_state_bytes.restype = C.c_size_t
+    lib.rtfe_ww_detector_initial_state.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+    lib.rtfe_ww_detector_scan.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t,
+                                          C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     lib.rtfe_scan_stats.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
     lib.rtfe_find_end_mark.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     lib.rtfe_pack_events.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
@@ -525,34 +535,66 @@ class FrontEnd:
         r._rows_keepalive = d_rows
         return r
 
-    # --- Whirlwind: the detector's state goes in and comes back (include/rt_frontend.h: rtfe_ww_scan) ---
-    WW_TRACK_BYTES = 224
+    # --- Whirlwind: the detector's state goes in and comes back (include/rt_frontend.h: rtfe_ww_scan, rtfe_ww_detector_scan) ---
+    WW_TRACK_BYTES = 224           # rtfe_ww_track: peak detection on the undifferentiated signal
+
+    @property
+    def ww_kind(self) -> int:
+        """The detector this handle runs on a Whirlwind tape (WW_PEAKS / WW_ZEROS / WW_DIFFZEROS / WW_DIFFPEAKS): the configuration decides."""
+        return int(self.lib.rtfe_ww_state_kind(self.h))
+
+    @property
+    def ww_track_bytes(self) -> int:
+        """Bytes of one track's state for this handle's detector."""
+        return int(self.lib.rtfe_ww_state_bytes(self.h))
+
+    @property
+    def ww_event_dtype(self):
+        return EVENT_DTYPE if self.ww_kind == WW_PEAKS else WW_EVENT_DTYPE
 
     def ww_initial_state(self) -> bytes:
-        buf = (C.c_ubyte * (self.WW_TRACK_BYTES * self.cfg.ntrks))()
-        self.lib.rtfe_ww_initial_state(buf, self.cfg.ntrks)
+        n = self.ww_track_bytes * self.cfg.ntrks
+        buf = (C.c_ubyte * n)()
+        if self.ww_kind == WW_PEAKS:
+            self.lib.rtfe_ww_initial_state(buf, self.cfg.ntrks)
+        else:
+            rc = self.lib.rtfe_ww_detector_initial_state(self.h, buf, n)
+            if rc != 0:
+                raise RuntimeError(f"rtfe_ww_detector_initial_state failed ({rc}): {self.lib.rtfe_last_error().decode()}")
         return bytes(buf)
 
     def ww_scan(self, rows, first_row, nscan, seed_row0, state: bytes, cap: int):
-        """-> (counts[ntrks], events[ntrks, cap] (EVENT_DTYPE, sample relative to first_row), state after the last row, flags)"""
+        """-> (counts[ntrks], events[ntrks, cap] (EVENT_DTYPE, or WW_EVENT_DTYPE for the zero-crossing / differentiated detectors; sample relative to
+        first_row), state after the last row, flags).  A state of another size than the handle's detector keeps is refused."""
         be, T = self.backend, self.cfg.ntrks
         d_rows = self._rows(rows)
+        peaks = self.ww_kind == WW_PEAKS
+        tb, edt = self.ww_track_bytes, self.ww_event_dtype
         b = self._cache.get(("ww", cap))
         if b is None:
-            b = self._cache[("ww", cap)] = dict(st_in=be.empty(T * self.WW_TRACK_BYTES), st_out=be.empty(T * self.WW_TRACK_BYTES), counts=be.empty(T * 4),
-                                                events=be.empty(T * cap * 16), flags=be.empty(16))
-        assert len(state) == T * self.WW_TRACK_BYTES
+            b = self._cache[("ww", cap)] = dict(st_in=be.empty(T * tb), st_out=be.empty(T * tb), counts=be.empty(T * 4),
+                                                events=be.empty(T * cap * edt.itemsize), flags=be.empty(16))
+        if len(state) != T * tb:
+            raise RuntimeError(f"a Whirlwind detector state of {len(state)} bytes: this front end's is {T * tb} ({T} tracks of {tb})")
         be.upload(b["st_in"], state)
         be.upload(b["flags"], b"\0" * 16)
-        rc = self.lib.rtfe_ww_scan(self.h, be.ptr(d_rows), int(d_rows.shape[0]), 0, int(first_row), int(nscan), int(seed_row0), be.ptr(b["st_in"]), be.ptr(b["st_out"]),
-                                   be.ptr(b["counts"]), be.ptr(b["events"]), int(cap), be.ptr(b["flags"]), be.stream())
+        if peaks:
+            name = "rtfe_ww_scan"
+            rc = self.lib.rtfe_ww_scan(self.h, be.ptr(d_rows), int(d_rows.shape[0]), 0, int(first_row), int(nscan), int(seed_row0), be.ptr(b["st_in"]), be.ptr(b["st_out"]),
+                                       be.ptr(b["counts"]), be.ptr(b["events"]), int(cap), be.ptr(b["flags"]), be.stream())
+        else:
+            name = "rtfe_ww_detector_scan"
+            rc = self.lib.rtfe_ww_detector_scan(self.h, be.ptr(d_rows), int(d_rows.shape[0]), 0, int(first_row), int(nscan), int(seed_row0), be.ptr(b["st_in"]),
+                                                be.ptr(b["st_out"]), T * tb, be.ptr(b["counts"]), be.ptr(b["events"]), int(cap), be.ptr(b["flags"]), be.stream())
         if rc != 0:
-            raise RuntimeError(f"rtfe_ww_scan failed ({rc}): {self.lib.rtfe_last_error().decode()}")
+            raise RuntimeError(f"{name} failed ({rc}): {self.lib.rtfe_last_error().decode()}")
         be.sync()
-        counts = be.to_numpy(b["counts"], np.uint32)[:T].copy()
-        events = be.to_numpy(b["events"], EVENT_DTYPE)[: T * cap].reshape(T, cap).copy()
-        st = bytes(be.to_numpy(b["st_out"], np.uint8)[: T * self.WW_TRACK_BYTES])
         flags = int(be.to_numpy(b["flags"], np.uint32)[0])
+        if flags & F_STATE_KIND:
+            raise RuntimeError(f"{name}: the state blob belongs to another detector than this front end's (kind {self.ww_kind})")
+        counts = be.to_numpy(b["counts"], np.uint32)[:T].copy()
+        events = be.to_numpy(b["events"], edt)[: T * cap].reshape(T, cap).copy()
+        st = bytes(be.to_numpy(b["st_out"], np.uint8)[: T * tb])
         return counts, events, st, flags
 
     # --- helpers that restate how the reference turns an event into times (src/decoder.c:732, src/readtape.c:1423) ---

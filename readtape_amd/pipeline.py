@@ -69,6 +69,7 @@ def _open_decode_lib():
     lib.rt_replay_run_after_deskew.argtypes = lib.rt_replay_run.argtypes
     lib.rt_replay_run_ww.argtypes = [C.POINTER(_Options), C.POINTER(_Parms), C.c_int64, C.c_int64, C.c_int64, C.c_int, _WW_SCAN_FN, C.c_void_p, C.c_void_p, C.c_int64,
                                      C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(_Stats), C.c_int, C.POINTER(C.c_int)]
+    lib.rt_replay_run_ww_detector.argtypes = lib.rt_replay_run_ww.argtypes[:9] + [C.c_size_t] + lib.rt_replay_run_ww.argtypes[9:]
     lib.rt_replay_run_named.argtypes = lib.rt_replay_run.argtypes[:15] + [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.POINTER(_Stats)]
     lib.rt_replay_run_fragment.argtypes = lib.rt_replay_run.argtypes + [C.c_int64, C.c_int64]
     lib.rt_replay_run_fragments.argtypes = lib.rt_replay_run.argtypes[:15] + [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(_Stats), C.POINTER(C.c_double)]
@@ -258,7 +259,8 @@ def decode_tape(hdr, rows, tap_path, log_path=None, opts: DecodeOptions | None =
     opts = opts or DecodeOptions()
     if hdr.mode == tbin.MODE_WW:                                           # one chain per tape, detector state handed back and forth: its own path
         st = decode_tape_ww(hdr, rows, tap_path, log_path=log_path, order=trkorder, verbose=opts.verbose, evt_path=evt_path, fe_factory=fe_factory,
-                            invert=invert, out_base=out_base, in_name=in_name, deskew=deskew, fluxdir=fluxdir, reverse=reverse)      # (-fluxdir, -reverse: Whirlwind only)
+                            invert=invert, out_base=out_base, in_name=in_name, deskew=deskew, fluxdir=fluxdir, reverse=reverse,      # (-fluxdir, -reverse: Whirlwind only)
+                            find_zeros=find_zeros, differentiate=differentiate)
         return st, None
     lib = _load_decode_lib()
     if trkorder:                                                           # -order= wins over the header's TBINORD extension (src/readtape.c:1346-1355)
@@ -347,12 +349,14 @@ FLUX = {"neg": 0, "pos": 1, "auto": 2}
 
 
 def decode_tape_ww(hdr, rows, tap_path, log_path=None, order: str | None = None, fluxdir: str = "neg", reverse: bool = False, verbose: bool = True,
-                   evt_path=None, fe_factory=None, invert=False, chunk_rows: int = 4096, out_base=None, in_name=None, deskew: bool = False):
+                   evt_path=None, fe_factory=None, invert=False, chunk_rows: int = 4096, out_base=None, in_name=None, deskew: bool = False,
+                   find_zeros: bool = False, differentiate: bool = False):
     """Decodes a Whirlwind tape (6 tracks, 100 BPI; mode WW in the header or by the caller).  order = the heads' roles (-order=CMLcml,
     default: the header's TBINORD string); fluxdir neg / pos / auto.  The device detector keeps its state across block attempts, so
     the host replay fetches its events in chunks and hands the state back in (rtfe_ww_scan).  deskew: the reference's
     -deskew (a pre-pass over the first blocks learns every head's delay and the pulse heights, src/readtape.c:1676-1716; the delays
-    come back as stats["skew_delays"]).  Returns the statistics."""
+    come back as stats["skew_delays"]).  find_zeros / differentiate: the reference's -zeros / -differentiate - the zero-crossing detectors and
+    the peak detector on the differentiated signal (rtfe_ww_detector_scan); the front end picks the state kind from them.  Returns the statistics."""
     lib = _load_decode_lib()
     order = order or hdr.trkorder or "CMLcml"
     if len(order) != hdr.ntrks:
@@ -370,17 +374,19 @@ def decode_tape_ww(hdr, rows, tap_path, log_path=None, order: str | None = None,
     full = default_parmsets(tbin.MODE_WW, 1)
     import dataclasses
     h2 = dataclasses.replace(hdr, mode=tbin.MODE_WW, bpi=bpi, ips=ips, trkorder="", flags=hdr.flags & ~tbin.FLAG_NO_REORDER)
-    cfg = frontend.FrontEndConfig.from_header(h2, parmsets=frontend_parmsets(full), invert=invert)
+    cfg = frontend.FrontEndConfig.from_header(h2, parmsets=frontend_parmsets(full), invert=invert, find_zeros=bool(find_zeros), differentiate=bool(differentiate))
     fe = (fe_factory or frontend.FrontEnd)(cfg)
-    o = _Options(mode=tbin.MODE_WW, ntrks=hdr.ntrks, bpi=bpi, ips=ips, specified_parity=1, revparity=0, do_correction=0, find_zeros=0, do_differentiate=0,
+    o = _Options(mode=tbin.MODE_WW, ntrks=hdr.ntrks, bpi=bpi, ips=ips, specified_parity=1, revparity=0, do_correction=0, find_zeros=int(bool(find_zeros)),
+                 do_differentiate=int(bool(differentiate)),
                  multiple_tries=0, tap_format=1, add_parity=0, verbose=int(verbose), ww_fluxdir=FLUX[fluxdir], ww_reverse=int(reverse), ww_order=order.encode())
     d_rows = fe.backend.rows(rows)
     cap = int(chunk_rows)
     bad = []
+    track_bytes = fe.ww_track_bytes
 
     def scan(user, first_row, nscan, seed_row0, state_in, state_out, counts_out, events_out, cap_in):
         try:
-            st_in = C.string_at(state_in, hdr.ntrks * fe.WW_TRACK_BYTES)
+            st_in = C.string_at(state_in, hdr.ntrks * track_bytes)
             counts, events, st, flags = fe.ww_scan(d_rows, first_row, nscan, seed_row0, st_in, int(cap_in))
             if flags & (frontend.F_DETECTOR_FATAL | frontend.F_EVENT_OVERFLOW):
                 bad.append(flags)
@@ -398,7 +404,7 @@ def decode_tape_ww(hdr, rows, tap_path, log_path=None, order: str | None = None,
     st = _Stats()
     init = fe.ww_initial_state()
     delays = (C.c_int * hdr.ntrks)()
-    rc = lib.rt_replay_run_ww(C.byref(o), (_Parms * 1)(full[0]), hdr.tdelta_ns, hdr.tstart_ns, int(d_rows.shape[0]), fe.widths[0], cb, None, init, cap,
+    rc = lib.rt_replay_run_ww_detector(C.byref(o), (_Parms * 1)(full[0]), hdr.tdelta_ns, hdr.tstart_ns, int(d_rows.shape[0]), fe.widths[0], cb, None, init, track_bytes, cap,
                               tap_path.encode() if tap_path and not out_base else None, out_base.encode() if out_base else None,
                               (in_name or "").encode() if (out_base and in_name) else None, log_path.encode() if log_path else None,
                               evt_path.encode() if evt_path else None, C.byref(st), int(bool(deskew)), delays)
@@ -406,7 +412,7 @@ def decode_tape_ww(hdr, rows, tap_path, log_path=None, order: str | None = None,
     if rc == -2 and not bad:
         raise RuntimeError("the -deskew pre-pass found tracks without flux transitions (is the order string right?)")
     if rc != 0:
-        raise RuntimeError(f"rt_replay_run_ww failed ({bad[:2]})")
+        raise RuntimeError(f"rt_replay_run_ww_detector failed ({rc}, {bad[:2]})")
     stats = {k: getattr(st, k) for k, _ in _Stats._fields_}
     if deskew:
         stats["skew_delays"] = list(delays)
