@@ -51,7 +51,8 @@ struct rtfe_handle {
    int bursts_wpr;                     // RTFE_BURSTS_WPR: words of the quiet map per round of the zone search (tests: many rounds on a short tape); 0 = 4096
    int sfs_occ[kMaxScreens];           // k_sift_s: workgroups of a screen's instantiation a CU holds at once (the occupancy API, at create)
    long long work_cap;      // RTFE_WORK_CAP
-   int ds_order, dchain_wgs, prep_wgs, dense_stop, dseg_wgs, dseg_threads;      // RTFE_DS_ORDER (0: chains in burst order), RTFE_DCHAIN_WGS / RTFE_PREP_WGS / RTFE_DSEG_WGS (workgroups per CU), RTFE_DENSE_STOP (debugging): read once, at create
+   long long ccap_max;      // RTFE_CCAP (tests)
+   int ds_order, dchain_wgs, prep_wgs, prep_run, dense_stop, dseg_wgs, dseg_threads;      // RTFE_DS_ORDER (0: chains in burst order), RTFE_DCHAIN_WGS / RTFE_PREP_WGS / RTFE_DSEG_WGS (workgroups per CU), RTFE_PREP_RUN (tiles a wave of k_prep), RTFE_DENSE_STOP (debugging): read once, at create
    // rtfe_set_graphs: a scan's launches (about twenty, on two streams) captured once per set of arguments into a HIP graph and replayed - what a scan of the same
    // buffers costs the host, and the gaps between its kernels on the device, shrink to one launch
    int graphs;
@@ -432,7 +433,10 @@ static int create_impl(const rtfe_config *c, rtfe_handle **out, int tile_overrid
    h->ds_order = getenv("RTFE_DS_ORDER") ? atoi(getenv("RTFE_DS_ORDER")) : 1;
    h->dchain_wgs = getenv("RTFE_DCHAIN_WGS") ? atoi(getenv("RTFE_DCHAIN_WGS")) : 16;
    h->prep_wgs = getenv("RTFE_PREP_WGS") ? atoi(getenv("RTFE_PREP_WGS")) : 32;
+   h->prep_run = getenv("RTFE_PREP_RUN") ? atoi(getenv("RTFE_PREP_RUN")) : 8;
+   if (h->prep_run < 1 || h->prep_run > kPrepMaxRun) h->prep_run = 8;
    h->work_cap = getenv("RTFE_WORK_CAP") ? atoll(getenv("RTFE_WORK_CAP")) : -1;
+   h->ccap_max = getenv("RTFE_CCAP") ? atoll(getenv("RTFE_CCAP")) : 0;
    h->dense_stop = getenv("RTFE_DENSE_STOP") ? atoi(getenv("RTFE_DENSE_STOP")) : 99;
    h->dseg_wgs = getenv("RTFE_DSEG_WGS") ? atoi(getenv("RTFE_DSEG_WGS")) : 0;
    h->dseg_threads = getenv("RTFE_DSEG_THREADS") ? atoi(getenv("RTFE_DSEG_THREADS")) : 0;
@@ -549,7 +553,9 @@ static long long pk_hard_cap(const rtfe_handle *h, int64_t nrows);
 // (a stream's capacity: every slot's worth of records and a marker per tile.  Deferred candidates add up to three records each; a stream
 //  that outgrows the capacity through them - its slots would have to be full of records without margins as well - is not built, and its
 //  chains give up)
-static long long pk_ccap(const rtfe_handle *h, int64_t nrows) { return pk_tiles_for(nrows) * (h->dev.pk_slot / 8 + 1) + 64; }
+static long long pk_ccap(const rtfe_handle *h, int64_t nrows) {      // (RTFE_CCAP: a smaller one, for the tests - streams that outgrow it are not built)
+   const long long c = pk_tiles_for(nrows) * (h->dev.pk_slot / 8 + 1) + 64;
+   return h->ccap_max > 0 && h->ccap_max < c ? h->ccap_max : c; }
 static size_t ws_pktstart_off(const rtfe_handle *h, int64_t nrows) { return ws_pkqtile_off(h, nrows) + pk_qtile_bytes(h, nrows); }
 static size_t pk_tstart_bytes(const rtfe_handle *h, int64_t nrows) {      // tile offsets | chunk totals | chunk offsets | stream totals
    const size_t nl = (size_t)h->dev.nscreens * h->dev.ntrks, nch = (size_t)(pk_tiles_for(nrows) + 1023) / 1024;
@@ -751,8 +757,9 @@ static int scan_launch(rtfe_handle *h, const int16_t *d_rows, int64_t nrows, int
                          (const int *)&scratch->hard_count, ovfp, extrap, scratch->dbg2);
       hipLaunchKernelGGL(k_pscan1, dim3(nsc), dim3(1024), 0, st, (const PeakDir *)dirm, (const int *)extrap, (int)ptiles, nlists, tstartp, ctotcp);
       hipLaunchKernelGGL(k_pscan2, dim3(1), dim3(1024), 0, st, nsc, nlists, (const uint32_t *)ctotcp, coffp, ctotp);
-      PrepArgs ppa; ppa.nlists = nlists; ppa.ntrks = h->dev.ntrks; ppa.hcap = h->dev.pk_slot; ppa.mv = h->dev.maxvolts;
-      // (workgroups per CU: 4 / 8 / 16 measured 0.51 / 0.47 / 0.42 ms for the span on C2 - half a wave per list, the more lists in flight the better)
+      PrepArgs ppa; ppa.nlists = nlists; ppa.ntrks = h->dev.ntrks; ppa.hcap = h->dev.pk_slot; ppa.run = h->prep_run; ppa.mv = h->dev.maxvolts;
+      // (workgroups per CU: 4 / 8 / 16 measured 0.51 / 0.47 / 0.42 ms for the span on C2 when half a wave took a list - the more lists in flight the better; a wave takes a
+      //  run of prep_run tiles of one stream now, RTFE_PREP_RUN, and 32 has not been tuned again for that shape)
       hipLaunchKernelGGL(k_prep, dim3(h->num_cus * (h->prep_wgs >= 1 && h->prep_wgs <= 4096 ? h->prep_wgs : 32)), dim3(256), 0, st, ppa, (const PeakDir *)dirm, (const unsigned char *)pkpool, (const unsigned char *)ovfp,
                          (const uint32_t *)tstartp, (const uint32_t *)coffp, (const uint32_t *)ctotp, ptiles, ccap, crecp, erefp,
                          reinterpret_cast<unsigned long long *>(wsb + ws_pkgfire_off(h, nrows)), pk_work_cap(h, nrows), &scratch->prep_work);
@@ -761,6 +768,8 @@ static int scan_launch(rtfe_handle *h, const int16_t *d_rows, int64_t nrows, int
                          (const uint32_t *)ctotp, ccap, crecp);
 #ifdef RTFE_CPU_EMUL
       if (getenv("RTFE_PREP_CHECK")) hipLaunchKernelGGL(k_prep_check, dim3(1), dim3(64), 0, st, (const DevCfg *)h->d_dev, (const uint32_t *)ctotp, ccap, (const CRec *)crecp);
+      if (getenv("RTFE_PREP_CHECK") && atoi(getenv("RTFE_PREP_CHECK")) > 1)
+         hipLaunchKernelGGL(k_prep_shapes, dim3(1), dim3(64), 0, st, nlists, (int)h->dev.pk_slot, h->prep_run, ptiles, ccap, (const PeakDir *)dirm, (const unsigned char *)pkpool, (const uint32_t *)ctotp);
 #endif
       t1(kTPrep);
       if (sa != st) (void)hipStreamWaitEvent(st, h->ev_join, 0);        // join: the chains need both

@@ -102,7 +102,7 @@ __device__ __forceinline__ long long chain_stop(const DevCfg &cfg, const rtfe_bu
 // k_pscan / k_prep: k_sift's lists (one fixed slot per tile and head) -> ONE contiguous stream of 16-byte records per (screen, head),
 // in row order, with everything a chain's lane would otherwise recompute per record on its critical path: the owner's absolute
 // row, volt() of its value, where its margin entries are.  k_pscan: the streams' tile offsets (a prefix sum per stream over the
-// tile directory); k_prep: a wave per list copies its records over.
+// tile directory); k_prep: a wave per run of a stream's tiles copies their records over.
 // ------------------------------------------------------------------------------------------------
 // flags in CRec::w0 bits 0-10 (the tile-relative row of PeakRec::w0 is replaced by the absolute CRec::pos)
 // (kCrBad / kCrClear / kCrWeak and the helpers that read them: rtfe_sift.hip, beside the records' layout - k_sift_hard makes kCrWeak for its records)
@@ -151,136 +151,163 @@ __device__ __forceinline__ int half_incl_scan(int v, int hl) {
 #endif
 }
 
-// k_prep: the tiles' lists -> the streams.  Half a wave per list (a clean NRZI tile holds ~21 records per head), the next list's
-// directory entry and records in flight while this one is written (a list is two dependent HBM round trips otherwise, and there is
-// little else to hide them).  Per record: its absolute row, its volts, its margin block, kCrWeak, and kCrClear where the record's successor in the stream (the
+// k_prep: the tiles' lists -> the streams.  A WAVE takes a run of `run` consecutive tiles of ONE stream (RTFE_PREP_RUN; a clean NRZI tile holds ~21 records per head)
+// and goes through the run's entries as one sequence, a lane per entry: one load brings the run's directory entries (and the one behind the run), then every lane
+// fetches exactly its own entry - no byte of a slot behind a list's end, each pool line once - and a record's successor, the next entry of the run whichever list it
+// is in, comes from the neighbouring lane.  Only the run's last record looks at the pool a second time (the first record of the tile behind the run).  A stream's
+// position behind the run's first tile is a running sum, counted as k_pscan1 counts.  (Until round 7: half a wave per list read 32 entries of the slot before it
+// knew the list's length, and the next tile's first record once more per list - 827 MB for C2's 347 MB of records.)
+// Per record: its absolute row, its volts, its margin block, kCrWeak, and kCrClear where the record's successor in the stream (the
 // list's next entry; the first of the next tile's list) settles it - the rest on a work list for k_clear (below).
 #ifdef RTFE_CPU_EMUL
 __device__ __forceinline__ int rtfe_uniform(int v) { return v; }
+__device__ __forceinline__ int rtfe_readlane(int v, int l) { return __shfl(v, l); }
 #else
 __device__ __forceinline__ int rtfe_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }      // a value every lane of the wave holds: into a scalar register
+__device__ __forceinline__ int rtfe_readlane(int v, int l) { return __builtin_amdgcn_readlane(v, l); }      // (l: the same in every lane)
 #endif
 constexpr int kPrepWorkChunk = 256;      // places of the work list a wave of k_prep takes at a time (a round puts up to 64 x 4 records on it)
-struct PrepArgs { int nlists, ntrks, hcap; float mv; };      // (by value: a wave's first loads do not wait for a read of the configuration block)
+constexpr int kPrepMaxRun = 32;          // tiles a run (their directory entries and the one behind them: a lane each)
+constexpr int kPrepBatch = 4;            // rounds of 63 entries whose loads are issued together (a run of 8 clean NRZI lists: ~170 entries)
+struct PrepArgs { int nlists, ntrks, hcap, run; float mv; };      // (by value: a wave's first loads do not wait for a read of the configuration block)
 __global__ void __launch_bounds__(256) k_prep(const PrepArgs pa, const PeakDir *__restrict__ dir, const unsigned char *__restrict__ pool,
                                               const unsigned char *__restrict__ ovf, const uint32_t *__restrict__ tstart, const uint32_t *__restrict__ coff,
                                               const uint32_t *__restrict__ ctot, long long ntiles, long long ccap, CRec *__restrict__ crec, uint2 *__restrict__ cmar,
                                               unsigned long long *__restrict__ work, long long work_cap, int *__restrict__ work_count) {
-   const int nlists = pa.nlists, hcap = pa.hcap;
+   const int nlists = pa.nlists, hcap = pa.hcap, R = pa.run;
    const float mv = pa.mv;
-   const int lane = threadIdx.x & 63, hl = lane & 31, hbase = lane & 32;
-   const long long nall = ntiles * nlists;
-   const long long stride = (long long)gridDim.x * 8;                     // lists per sweep: four waves, two lists each
-   struct Pre { PeakDir d, dn; uint2 r, r1, rn, m; uint32_t ts, co, ct; };
-   auto fetch = [&](long long l, long long tl, int s2) -> Pre {      // (everything the list's step reads, bar a deferred candidate's records: no load inside the step to wait for)
-      Pre p; p.d.nrec = 0; p.d.nent = 0; p.dn = p.d; p.r = make_uint2(0, 0); p.r1 = p.r; p.rn = p.r; p.m = p.r; p.ts = 0; p.co = 0; p.ct = 0;
-      if (l < nall) {
-         const unsigned char *slot = pool + (size_t)l * hcap;
-         p.d = dir[l];
-         p.ts = tstart[(size_t)tl * nlists + s2]; p.co = coff[(size_t)(tl >> 10) * nlists + s2]; p.ct = ctot[s2];
-         {  const uint4 r4 = *reinterpret_cast<const uint4 *>(slot + min(16 * hl, hcap - 16));      // (16 bytes: the record, its margin block behind it)
-            p.r = make_uint2(r4.x, r4.y); p.m = make_uint2(r4.z, r4.w); }
-         p.r1 = *reinterpret_cast<const uint2 *>(slot + min(16 * (hl + 1), hcap - 16));
-         if (l + nlists < nall) { p.dn = dir[l + nlists]; p.rn = *reinterpret_cast<const uint2 *>(slot + (size_t)nlists * hcap); } }
-      return p; };
+   const int lane = threadIdx.x & 63, lnext = (lane + 1) & 63;
    const unsigned wcap = (unsigned)work_cap;                             // (< 2^31; a count that ran over reads as a place behind it)
    int wk_next = 0, wk_end = 0;                                          // the wave's places on the work list (k_clear); wave-uniform (work_cap < 2^31: the host)
-   long long li = (long long)blockIdx.x * 8 + (threadIdx.x >> 5);
-   // (tile, stream) of the list, stepped along with li: no division in the loop
+   // the runs: run * nlists + stream, the streams of one run of tiles side by side - a workgroup's four waves read the same lines of the directory
+   const long long nwork = ((ntiles + R - 1) / R) * nlists;
+   const long long stride = (long long)gridDim.x * 4;                     // runs per sweep: four waves a workgroup
+   long long wi = (long long)blockIdx.x * 4 + rtfe_uniform((int)(threadIdx.x >> 6));
+   // (run, stream), stepped along with wi: no division in the loop
    const long long dq = stride / nlists;
    const int dr = (int)(stride - dq * nlists);
-   long long tile = li / nlists;
-   int sl = (int)(li - tile * nlists);
-   // (no software prefetch of the next list: gfx9 counts loads and stores in ONE counter, the stores of a list's records are conditional, and
-   //  hipcc then waits for everything in flight before the first use of a prefetched value - measured: the loads of list i + 1 were waited for
-   //  right behind their issue.  Eight waves per SIMD hide the round trip instead: the registers the second set of values took are free.)
-   for (; __ballot(li < nall) != 0ull; li += stride, tile += dq, sl += dr) {
-      if (sl >= nlists) { sl -= nlists; ++tile; }
-      const Pre cu = fetch(li, tile, sl);
-      const PeakDir d = cu.d;
-      const bool on = li < nall && d.nrec != 0;
-      const bool built = on && (long long)cu.ct <= ccap;                  // a stream that outgrew its capacity is not built: its chains give up (k_gain)
-      long long base = built ? (long long)sl * ccap + (long long)cu.ts + (long long)cu.co : 0;
-      if (built && d.nrec == 0xffffu) {                                  // a list that did not fit: one marker at the tile's first row
-         if (hl == 0) { CRec m; m.pos = (uint32_t)(tile * kSfTile); m.w0 = kCrBad | (1u << 12); m.w1 = 0xffff8000u; m.volt = 0; crec[base] = m; cmar[base] = make_uint2(0, 0); } }
-      const int nrec = (built && d.nrec != 0xffffu) ? (int)d.nrec : 0;
-      const unsigned char *slot = pool + (size_t)(on ? li : 0) * hcap;
-      const long long pos0 = tile * kSfTile - kSfPosBias;
+   long long run = wi / nlists;
+   int sl = (int)(wi - run * nlists);
+   // (no software prefetch of the next run: gfx9 counts loads and stores in ONE counter, the stores of a round's records are conditional, and
+   //  hipcc then waits for everything in flight before the first use of a prefetched value.  Seven waves per SIMD hide the round trips instead.)
+   for (; wi < nwork; wi += stride, run += dq, sl += dr) {
+      if (sl >= nlists) { sl -= nlists; ++run; }
+      const long long t0 = run * R;
+      const int nt = (int)min((long long)R, ntiles - t0);                // tiles of this run
+      // lane i: the directory entry of tile t0 + i; lane nt: the tile behind the run - the successor of the run's last record is its first
+      uint32_t nraw = 0; uint2 rn = make_uint2(0, 0);
+      if (lane <= nt && t0 + lane < ntiles) {
+         const size_t l = (size_t)(t0 + lane) * nlists + sl;
+         nraw = dir[l].nrec;
+         if (lane == nt) rn = *reinterpret_cast<const uint2 *>(pool + l * hcap); }
+      const uint32_t ct = ctot[sl];
+      long long base = (long long)sl * ccap + (long long)tstart[(size_t)t0 * nlists + sl] + (long long)coff[(size_t)(t0 >> 10) * nlists + sl];
+      if ((long long)ct > ccap) continue;                                 // a stream that outgrew its capacity is not built: its chains give up (k_gain)
+      // the run's entries 0 .. T - 1: a list's records; ONE for a list that did not fit (nrec == 0xffff: it becomes a marker at the tile's first row)
+      const int ne = lane < nt ? (nraw == 0xffffu ? 1 : (int)nraw) : 0;
+      const int incl = wave_incl_scan(ne, lane), excl = incl - ne;
+      const int T = wave_last(incl);
+      const uint32_t pk = nraw | ((uint32_t)__shfl((int)nraw, lnext) << 16);      // the list's length, the next tile's list's
+      const uint32_t rnx = (uint32_t)rtfe_readlane((int)rn.x, nt), rny = (uint32_t)rtfe_readlane((int)rn.y, nt);
       // kCrClear: nothing behind the record in its stream has a row at or before X, the last row the record can fire at.  A stream is in the order of its
       // CANDIDATES and a candidate's records have their rows behind the candidate, so the look ahead from the record ends - yes - at the first record whose candidate (its owner at
       // the least) lies at or behind X; every record it passes on the way must begin behind X.  The successor settles it nine times in ten: a plain entry of this list - or the first
-      // of the next tile's - straight from the registers.  What it does not settle, and the records of deferred candidates, go on a work list: k_clear looks ahead in the finished
+      // of the next tile's - straight from the neighbouring lane.  What it does not settle, and the records of deferred candidates, go on a work list: k_clear looks ahead in the finished
       // stream (the loop in here, beside the records' registers, cost k_prep two waves a SIMD: 0.33 -> 0.43 ms on C2).
       // (Rounds 3 - 6a asked this of the record's successor alone: a bottom whose successor - the next bottom - began behind its window was marked although the top between those
       //  two, the record after next, fired at the very row the bottom did, and tops go first: tools/fuzz_shapes.py.)
-      const int nrec_l = (on && d.nrec != 0xffffu) ? (int)d.nrec : 0;
-      const int p32 = (int)pos0;                                           // (rows in 32 bits: rtfe_scan hands this path fragments of less than 2^31 rows)
-      int rounds = (nrec + 31) >> 5;
-      {  const int other = __shfl(rounds, lane ^ 32); if (other > rounds) rounds = other; }      // (both halves run the scans of every round)
-      for (int rd = 0; rd < rounds; ++rd) {
-         const int k = rd * 32 + hl;
-         const bool have = k < nrec;
-         uint2 q = cu.r, q1 = cu.r1;
-         if (rd > 0 && have) { q = *reinterpret_cast<const uint2 *>(slot + 16 * k); if (k + 1 < nrec) q1 = *reinterpret_cast<const uint2 *>(slot + 16 * (k + 1)); }
-         const uint32_t w0 = have ? q.x : 0u, w1 = have ? q.y : 0u;
-         const bool deferred = have && w1 == 0xffff8001u;                  // its records are in overflow slot w0 (k_sift_hard): they take its place
-         const unsigned char *os = ovf + (size_t)(deferred ? w0 : 0u) * kSfOvfBytes;
-         const int cnt = deferred ? *reinterpret_cast<const int *>(os) : (have ? 1 : 0);
-         const int ic = half_incl_scan(cnt, hl);
-         const long long o = base + ic - cnt;
-         uint32_t todo = 0;                                                // bit j: record j of this entry goes on the work list
-         if (deferred) {
-            // (a stale minimum's record is owned by a sample in front of its candidate: further than two rows in front, the countdown it leaves when it fires ends before
-            //  the rows of a record the chain has passed over do - such a record is never marked: it is the general step's, which looks back - k_gain)
-            const int qrel = kSfPosBias + *reinterpret_cast<const int *>(os + 4);
-            #pragma nounroll
-            for (int j = 0; j < cnt; ++j) {
-               const uint2 e = *reinterpret_cast<const uint2 *>(os + 8 + 16 * j);
-               const uint2 em = *reinterpret_cast<const uint2 *>(os + 8 + 16 * j + 8);
-               const uint32_t ew = *reinterpret_cast<const uint32_t *>(os + 72 + 4 * j);      // (kCrWeak and its bits: k_sift_hard made them beside the margins - made here, they cost k_prep 22 registers)
-               CRec c; c.pos = (uint32_t)(pos0 + (long long)(e.x & 0x7ffu)); c.w0 = (e.x & ~0x7ffu) | ew; c.w1 = e.y; c.volt = volt((int)(int16_t)(e.y & 0xffffu), mv);
-               if (crec_can_clear(e.x, e.y, ew) && qrel <= (int)(e.x & 0x7ffu) + 2) todo |= 1u << j;
-               crec[o + j] = c;
-               cmar[o + j] = em; } }
-         else if (have) {
-            uint2 mk2 = cu.m;                                              // (its margin block: with the record in the first round)
-            if (rd > 0) mk2 = *reinterpret_cast<const uint2 *>(slot + 16 * k + 8);
-            const uint32_t wk = crec_weak_bits(w0, w1, mk2);
-            CRec c; c.pos = (uint32_t)(pos0 + (long long)(w0 & 0x7ffu)); c.w0 = (w0 & ~0x7ffu) | wk; c.w1 = w1; c.volt = volt((int)(int16_t)(w1 & 0xffffu), mv);
-            if (crec_can_clear(w0, w1, wk)) {
-               const int X = p32 + (int)(w0 & 0x7ffu) + (int)((w0 >> 12) & 63u) + (int)((w0 >> 18) & 15u) - (wk ? 1 : 0);      // the first sure row; kCrWeak: its last row
-               // its successor: the list's next entry, the next tile's first, none
-               uint2 sq = q1; int sp0 = p32; int kind = 0;                 // 0: an entry, 1: nothing behind it that could matter, 2: cannot tell from here
-               if (k + 1 >= nrec_l) {
-                  const int nn = (int)cu.dn.nrec;
-                  if (tile + 1 >= ntiles || nn == 0) kind = 1;              // (the stream ends; an empty list: two lists on, and a tile is longer than a window)
-                  else if (nn == 0xffff) kind = p32 + kSfPosBias + kSfTile >= X ? 1 : 3;      // a list that is not there: whatever its tile holds has its rows behind the tile's first
-                  else { sq = cu.rn; sp0 = p32 + kSfTile; } }
-               if (kind == 0) {
-                  if (sq.y == 0xffff8001u) kind = 2;
-                  else {
-                     const int pj = sp0 + (int)(sq.x & 0x7ffu);
-                     if (pj + (int)((sq.x >> 12) & 63u) <= X) kind = 3;     // (3: not clear)
-                     else kind = pj >= X ? 1 : 2; } }
-               if (kind == 1) c.w0 |= kCrClear;
-               if (kind == 2) todo = 1u; }
-            crec[o] = c;
-            cmar[o] = mk2; }
-         // the work list: a wave takes its places a chunk at a time (one atomic per record and wave round on ONE address: a 60 mV-noise tape's 1.2 M deferred candidates made
-         // k_prep 5 ms longer - as k_sift_s's list of deferred candidates had, before it took chunks); what it leaves of a chunk it marks empty
-         if (__ballot(todo != 0u) != 0ull) {
-            const int nt = __popc(todo);
-            const int incl = wave_incl_scan(nt, lane);
-            const int total = wave_last(incl);
-            if (wk_next + total > wk_end) {
-               for (int x = wk_next + lane; x < wk_end; x += 64) if ((unsigned)x < wcap) work[x] = ~0ull;
-               int nb = 0;
-               if (lane == 0) nb = atomicAdd(work_count, kPrepWorkChunk);
-               wk_next = rtfe_uniform(__shfl(nb, 0)); wk_end = wk_next + kPrepWorkChunk; }
-            int wbase = wk_next + incl - nt;
-            wk_next = rtfe_uniform(wk_next + total);
-            for (int j = 0; j < 4; ++j) if (todo & (1u << j)) { if ((unsigned)wbase < wcap) work[wbase] = (unsigned long long)(o + j); ++wbase; } }
-         base += __shfl(ic, hbase + 31); } }
+      // A round: lanes 0 - 62 take an entry each, lane 63 only fetches the entry behind them (the next round's first) for lane 62 to look at.
+      for (int f0 = 0; f0 < T; f0 += 63 * kPrepBatch) {
+         // which list an entry is in: the lists whose ends lie at or in front of it
+         int jj[kPrepBatch];
+         #pragma unroll
+         for (int u = 0; u < kPrepBatch; ++u) jj[u] = 0;
+         for (int i = 0; i + 1 < nt; ++i) {
+            const int e = rtfe_readlane(incl, i);
+            #pragma unroll
+            for (int u = 0; u < kPrepBatch; ++u) jj[u] += (f0 + u * 63 + lane >= e) ? 1 : 0; }
+         uint4 q[kPrepBatch];                                              // (16 bytes: the record, its margin block behind it)
+         #pragma unroll
+         for (int u = 0; u < kPrepBatch; ++u) {
+            const int f = f0 + u * 63 + lane;
+            const int k = f - __shfl(excl, jj[u]);
+            const uint32_t nr = (uint32_t)__shfl((int)pk, jj[u]) & 0xffffu;
+            q[u] = make_uint4(0, 0, 0, 0);
+            if (f < T && nr != 0xffffu) q[u] = *reinterpret_cast<const uint4 *>(pool + ((size_t)(t0 + jj[u]) * nlists + sl) * hcap + min(16 * k, hcap - 16));
+            else if (f == T) { q[u].x = rnx; q[u].y = rny; } }
+         #pragma unroll
+         for (int u = 0; u < kPrepBatch; ++u) {
+            if (f0 + u * 63 >= T) break;
+            const int f = f0 + u * 63 + lane;
+            const int k = f - __shfl(excl, jj[u]);
+            const uint32_t pkj = (uint32_t)__shfl((int)pk, jj[u]);
+            const int nrec_l = (int)(pkj & 0xffffu), nn = (int)(pkj >> 16);
+            const bool have = lane < 63 && f < T;
+            const uint2 sq0 = make_uint2((uint32_t)__shfl((int)q[u].x, lnext), (uint32_t)__shfl((int)q[u].y, lnext));      // the entry behind this one
+            const long long tile = t0 + jj[u];
+            const long long pos0 = tile * kSfTile - kSfPosBias;
+            const int p32 = (int)pos0;                                        // (rows in 32 bits: rtfe_scan hands this path fragments of less than 2^31 rows)
+            const bool marker = have && nrec_l == 0xffff;
+            const bool rec = have && !marker;
+            const uint32_t w0 = rec ? q[u].x : 0u, w1 = rec ? q[u].y : 0u;
+            const bool deferred = rec && w1 == 0xffff8001u;                   // its records are in overflow slot w0 (k_sift_hard): they take its place
+            const unsigned char *os = ovf + (size_t)(deferred ? w0 : 0u) * kSfOvfBytes;
+            const int cnt = deferred ? *reinterpret_cast<const int *>(os) : (have ? 1 : 0);
+            const int ic = wave_incl_scan(cnt, lane);
+            const long long o = base + ic - cnt;
+            uint32_t todo = 0;                                                // bit j: record j of this entry goes on the work list
+            if (marker) {                                                     // a list that did not fit: one marker at the tile's first row
+               CRec m; m.pos = (uint32_t)(tile * kSfTile); m.w0 = kCrBad | (1u << 12); m.w1 = 0xffff8000u; m.volt = 0; crec[o] = m; cmar[o] = make_uint2(0, 0); }
+            else if (deferred) {
+               // (a stale minimum's record is owned by a sample in front of its candidate: further than two rows in front, the countdown it leaves when it fires ends before
+               //  the rows of a record the chain has passed over do - such a record is never marked: it is the general step's, which looks back - k_gain)
+               const int qrel = kSfPosBias + *reinterpret_cast<const int *>(os + 4);
+               #pragma nounroll
+               for (int j = 0; j < cnt; ++j) {
+                  const uint2 e = *reinterpret_cast<const uint2 *>(os + 8 + 16 * j);
+                  const uint2 em = *reinterpret_cast<const uint2 *>(os + 8 + 16 * j + 8);
+                  const uint32_t ew = *reinterpret_cast<const uint32_t *>(os + 72 + 4 * j);      // (kCrWeak and its bits: k_sift_hard made them beside the margins - made here, they cost k_prep 22 registers)
+                  CRec c; c.pos = (uint32_t)(pos0 + (long long)(e.x & 0x7ffu)); c.w0 = (e.x & ~0x7ffu) | ew; c.w1 = e.y; c.volt = volt((int)(int16_t)(e.y & 0xffffu), mv);
+                  if (crec_can_clear(e.x, e.y, ew) && qrel <= (int)(e.x & 0x7ffu) + 2) todo |= 1u << j;
+                  crec[o + j] = c;
+                  cmar[o + j] = em; } }
+            else if (rec) {
+               const uint2 mk2 = make_uint2(q[u].z, q[u].w);                  // (its margin block: with the record)
+               const uint32_t wk = crec_weak_bits(w0, w1, mk2);
+               CRec c; c.pos = (uint32_t)(pos0 + (long long)(w0 & 0x7ffu)); c.w0 = (w0 & ~0x7ffu) | wk; c.w1 = w1; c.volt = volt((int)(int16_t)(w1 & 0xffffu), mv);
+               if (crec_can_clear(w0, w1, wk)) {
+                  const int X = p32 + (int)(w0 & 0x7ffu) + (int)((w0 >> 12) & 63u) + (int)((w0 >> 18) & 15u) - (wk ? 1 : 0);      // the first sure row; kCrWeak: its last row
+                  // its successor: the list's next entry, the next tile's first, none
+                  int sp0 = p32; int kind = 0;                                // 0: an entry, 1: nothing behind it that could matter, 2: cannot tell from here
+                  if (k + 1 >= nrec_l) {
+                     if (nn == 0) kind = 1;                                   // (the stream ends; an empty list: two lists on, and a tile is longer than a window)
+                     else if (nn == 0xffff) kind = p32 + kSfPosBias + kSfTile >= X ? 1 : 3;      // a list that is not there: whatever its tile holds has its rows behind the tile's first
+                     else sp0 = p32 + kSfTile; }
+                  if (kind == 0) {
+                     if (sq0.y == 0xffff8001u) kind = 2;
+                     else {
+                        const int pj = sp0 + (int)(sq0.x & 0x7ffu);
+                        if (pj + (int)((sq0.x >> 12) & 63u) <= X) kind = 3;  // (3: not clear)
+                        else kind = pj >= X ? 1 : 2; } }
+                  if (kind == 1) c.w0 |= kCrClear;
+                  if (kind == 2) todo = 1u; }
+               crec[o] = c;
+               cmar[o] = mk2; }
+            // the work list: a wave takes its places a chunk at a time (one atomic per record and wave round on ONE address: a 60 mV-noise tape's 1.2 M deferred candidates made
+            // k_prep 5 ms longer - as k_sift_s's list of deferred candidates had, before it took chunks); what it leaves of a chunk it marks empty
+            if (__ballot(todo != 0u) != 0ull) {
+               const int ntd = __popc(todo);
+               const int incl2 = wave_incl_scan(ntd, lane);
+               const int total = wave_last(incl2);
+               if (wk_next + total > wk_end) {
+                  for (int x = wk_next + lane; x < wk_end; x += 64) if ((unsigned)x < wcap) work[x] = ~0ull;
+                  int nb = 0;
+                  if (lane == 0) nb = atomicAdd(work_count, kPrepWorkChunk);
+                  wk_next = rtfe_uniform(__shfl(nb, 0)); wk_end = wk_next + kPrepWorkChunk; }
+               int wbase = wk_next + incl2 - ntd;
+               wk_next = rtfe_uniform(wk_next + total);
+               for (int j = 0; j < 4; ++j) if (todo & (1u << j)) { if ((unsigned)wbase < wcap) work[wbase] = (unsigned long long)(o + j); ++wbase; } }
+            base += wave_last(ic); } } }
    for (int x = wk_next + lane; x < wk_end; x += 64) if ((unsigned)x < wcap) work[x] = ~0ull; }
 
 // k_clear: kCrClear for the records k_prep could not settle from a record's successor - a thread per work list entry looks ahead in the finished stream.  Every record behind
@@ -337,6 +364,30 @@ __global__ void __launch_bounds__(64) k_prep_check(const DevCfg *__restrict__ cf
             const long long fj = (long long)r[j].pos + (long long)((r[j].w0 >> 12) & 63u);
             if (fj <= X) fprintf(stderr, "prep_check: stream %d record %lld pos %u marked clear (fires by row %lld), record %lld pos %u begins at row %lld\n", sl, i, r[i].pos, X, j, r[j].pos, fj); } } }
    if (getenv("RTFE_PREP_CHECK") && atoi(getenv("RTFE_PREP_CHECK")) > 1) fprintf(stderr, "prep_check: %lld of %lld records marked clear\n", nclear, nall); }
+// (emulator only, RTFE_PREP_CHECK > 1: which of the seams of k_prep's runs a tape's lists have - counted from the directory and the pool alone, for the tests that
+//  must know that their tapes reach them.  A run: `run` consecutive tiles of a stream; "behind a run": the first tile of the next one.  markers_*: lists that did
+//  not fit; marker_*: those of them that the last record of a list in front looks at.)
+__global__ void __launch_bounds__(64) k_prep_shapes(int nlists, int hcap, int run, long long ntiles, long long ccap, const PeakDir *__restrict__ dir, const unsigned char *__restrict__ pool,
+                                                    const uint32_t *__restrict__ ctot) {
+   if (blockIdx.x != 0 || threadIdx.x != 0) return;
+   long long empty_in = 0, empty_last = 0, longl = 0, mark_in = 0, mark_behind = 0, def_in = 0, def_list = 0, def_run = 0, over = 0, mk_in = 0, mk_behind = 0;
+   for (int sl = 0; sl < nlists; ++sl) {
+      if ((long long)ctot[sl] > ccap) ++over;
+      for (long long t = 0; t < ntiles; ++t) {
+         const size_t l = (size_t)t * nlists + sl;
+         const int n = dir[l].nrec, at = (int)(t % run);
+         const int np = t > 0 ? (int)dir[l - nlists].nrec : 0;            // the list in front: has it a last record that looks at this one?
+         const bool pred = np != 0 && np != 0xffff;
+         if (n == 0) { if (at == run - 1) ++empty_last; else if (t + 1 < ntiles) ++empty_in; continue; }
+         if (n == 0xffff) { if (at == 0 && t > 0) ++mk_behind; else if (at != 0) ++mk_in; if (pred) { if (at == 0) ++mark_behind; else ++mark_in; } continue; }
+         if (n > 32) ++longl;
+         const uint2 *e = reinterpret_cast<const uint2 *>(pool + l * hcap);
+         for (int k = 0; k < n; ++k) {
+            if (e[2 * k].y != 0xffff8001u) continue;
+            if (k > 0) { if (e[2 * (k - 1)].y != 0xffff8001u) ++def_in; }
+            else if (pred && reinterpret_cast<const uint2 *>(pool + (l - nlists) * hcap)[2 * (np - 1)].y != 0xffff8001u) { if (at == 0) ++def_run; else ++def_list; } } } }
+   fprintf(stderr, "prep_shapes: run %d tiles %lld empty_in %lld empty_last %lld long %lld marker_in %lld marker_behind %lld deferred_in %lld deferred_list %lld deferred_run %lld over_ccap %lld markers_in %lld markers_behind %lld\n",
+           run, ntiles, empty_in, empty_last, longl, mark_in, mark_behind, def_in, def_list, def_run, over, mk_in, mk_behind); }
 #endif
 
 // ------------------------------------------------------------------------------------------------
