@@ -234,7 +234,7 @@ const char *rtfe_kernel_name(int i);
  *   maxv/minv/countdown = 0, v_avg_height and delay set per track in the blob, and the decode from row 0.
  * Replaces: the per-sample lookfor_peak of src/decoder.c:751-810 for mode WW, at the seam of src/decoder.c:586,604. */
 typedef struct rtfe_ww_track {
-   int16_t ring[64];                /* pkww_v as int16 codes (after -invert) */
+   int16_t ring[64];                /* pkww_v as int16 codes (after -invert; there -32768 stands for +32768, the inverted -32768) */
    int32_t left, right, maxv, minv, countdown, peakcount, heightndx;
    int32_t delay;                   /* -deskew: this track's delay in samples (0..50; the FIFO of src/decoder.c:820-830 starts at row 0 of the tape) */
    float   agc_gain, v_avg_height, v_lasttop, v_lastbot, v_top, v_bot;

@@ -737,9 +737,12 @@ static int scan_launch(rtfe_handle *h, const int16_t *d_rows, int64_t nrows, int
       hipLaunchKernelGGL(k_qpack, dim3(h->num_cus < 64 ? h->num_cus : 64), dim3(256), 0, sa, (const uint16_t *)qtile, ptiles, qwords, nwords);
       launch_bursts(h, sa, qwords, nwords, nchunks, nrows, own_rows, first_is_tape_start, event_capacity, d_bursts,
                     (long long)(max_bursts < rtfe_max_bursts(h, nrows) ? max_bursts : rtfe_max_bursts(h, nrows)), scratch, d_nbursts, reinterpret_cast<uint32_t *>(wsb + ws_rtot_off(h, nrows)));
-      if (stop_after >= 3)
+      if (stop_after >= 3) {
          hipLaunchKernelGGL(k_zones, dim3(h->num_cus * 8), dim3(64), 0, sa, h->d_dev, d_rows, (long long)nrows, (const rtfe_burst *)d_bursts,
                             (const BurstScratch *)scratch, ctlp);
+         if (h->dev.invert)      // (an inverted -32768 is +32768, wider than a record: bursts that hold one go to the sample path's literal walk)
+            hipLaunchKernelGGL(k_rails, dim3(h->num_cus * 8), dim3(64), 0, sa, h->d_dev, d_rows, (long long)nrows, (const rtfe_burst *)d_bursts,
+                               (const BurstScratch *)scratch, ctlp); }
       t1s(kTBursts, sa);
       if (sa != st) (void)hipEventRecord(h->ev_join, sa);
       // the lists -> one stream of 16-byte records per (screen, head): the deferred candidates resolved (k_sift_hard), the streams' tile
@@ -846,9 +849,12 @@ static int scan_launch(rtfe_handle *h, const int16_t *d_rows, int64_t nrows, int
    t0(kTBursts);
    launch_bursts(h, st, qwords, nwords, nchunks, nrows, own_rows, first_is_tape_start, event_capacity, d_bursts,
                  (long long)(max_bursts < rtfe_max_bursts(h, nrows) ? max_bursts : rtfe_max_bursts(h, nrows)), scratch, d_nbursts, reinterpret_cast<uint32_t *>(wsb + ws_rtot_off(h, nrows)));
-   if (h->dev.dense_path)                                              // the restart rows of all bursts (rtfe_gain.hip)
+   if (h->dev.dense_path) {                                            // the restart rows of all bursts (rtfe_gain.hip)
       hipLaunchKernelGGL(k_zones, dim3(h->num_cus * 8), dim3(64), 0, st, h->d_dev, d_rows, (long long)nrows, (const rtfe_burst *)d_bursts,
                          (const BurstScratch *)scratch, ctlp);
+      if (h->dev.invert)
+         hipLaunchKernelGGL(k_rails, dim3(h->num_cus * 8), dim3(64), 0, st, h->d_dev, d_rows, (long long)nrows, (const rtfe_burst *)d_bursts,
+                            (const BurstScratch *)scratch, ctlp); }
    t1(kTBursts);
    if (h->dev.find_zeros && !h->dev.differentiate && h->zeros_kernel) {          // -zeros: the lean kernel of its own (rtfe_zeros.hip)
       t0(kTZeros);

@@ -99,6 +99,21 @@ __device__ __forceinline__ long long chain_stop(const DevCfg &cfg, const rtfe_bu
    return stop; }
 
 // ------------------------------------------------------------------------------------------------
+// k_rails (-invert only): the bursts whose rows hold the code -32768.  The reference negates the VOLTAGE (src/readtape.c:1421), so that sample is
+// +32768 - a code no int16 holds, and records, margins, packed lanes and the dense path's slots are all 16 bits wide.  Such a burst goes to the
+// sample path's literal walk (k_decode: burst_has_rail finds the same samples in the same rows), which reads it as what it is; the others
+// keep their chains.  A wave per burst, behind k_zones (a burst's rows end where the next one restarts).
+// ------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(64) k_rails(const DevCfg *__restrict__ cfgp, const int16_t *__restrict__ rows, long long nrows,
+                                              const rtfe_burst *__restrict__ bursts, const BurstScratch *__restrict__ scratch, BurstCtl *__restrict__ ctl) {
+   const DevCfg &cfg = *cfgp;
+   const int nb = scratch->nbursts;
+   for (int b = blockIdx.x; b < nb; b += gridDim.x) {
+      if (ctl[b].status != kBurstReady) continue;
+      const bool hit = rail_scan_lane(rows, cfg.ntrks, nrows, ctl[b].reset, chain_stop(cfg, bursts, ctl, b, scratch->nbursts_total, nrows), (int)threadIdx.x, 64);      // (the scan k_decode's burst_has_rail makes of the same rows)
+      if (__ballot(hit) != 0ull && threadIdx.x == 0) ctl[b].status = kBurstNeedsFull; } }
+
+// ------------------------------------------------------------------------------------------------
 // k_pscan / k_prep: k_sift's lists (one fixed slot per tile and head) -> ONE contiguous stream of 16-byte records per (screen, head),
 // in row order, with everything a chain's lane would otherwise recompute per record on its critical path: the owner's absolute
 // row, volt() of its value, where its margin entries are.  k_pscan: the streams' tile offsets (a prefix sum per stream over the

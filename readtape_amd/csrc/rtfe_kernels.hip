@@ -425,11 +425,12 @@ struct Tile {
    int      ntrks;
    const int *skew;
    float   *fd;           // LDS (-differentiate peak path only): differentiate()'s output for every element of x
+   int      rail;         // the code that stands for +32768 in x (zc_rail: -32768 in an inverted tile, else no sample)
    __device__ __forceinline__ float fy(int t, long long n) const {       // the detector's input at row n: differentiated, then deskewed
       const int d = skew[t];
       const long long m = (n - reset < d) ? n : n - d;
       return fd[((int)(m - row0) + halo) * ntrks + colof[t]]; }
-   __device__ __forceinline__ int xi(int t, long long n) const { return x[((int)(n - row0) + halo) * ntrks + colof[t]]; }
+   __device__ __forceinline__ int xi(int t, long long n) const { const int v = x[((int)(n - row0) + halo) * ntrks + colof[t]]; return v == rail ? 32768 : v; }
    // v_now of track t at row n in int16 units, with the deskew FIFO exactly as the reference runs it
    // from the restart row: undelayed until the FIFO has filled (src/decoder.c:825-827), then delayed
    __device__ __forceinline__ int y(int t, long long n) const {
@@ -474,7 +475,9 @@ __device__ __forceinline__ float volt(int i, float maxvolts) {      // src/readt
    return (float)i / 32767 * maxvolts; }
 // -invert negates the VOLTAGE: -volt(-32768) = volt(+32768), a code no int16 holds; load_tile's 16-bit negation leaves -32768 as it
 // was.  In an inverted tile nothing else negates to -32768, so there that code reads +32768 (rail = -32768; not inverted: rail = 1 << 30,
-// no sample).  The zero-crossing detectors read their samples through this; the peak path does not
+// no sample).  Tile::xi / Tile::y, the zero-crossing walks and differentiate_tile read their samples through this.  The peak detector's
+// screened walk (screen_strip's maps, eval_at's columns) and the record paths in front of it stay on 16 bits: a burst that holds such
+// a sample is walked literally instead (burst_has_rail, walk's `literal`)
 __device__ __forceinline__ int zc_rail(const DevCfg *cfg) { return cfg->invert ? -32768 : (1 << 30); }
 __device__ __forceinline__ int zc_code(int v, int rail) { return v == rail ? 32768 : v; }
 
@@ -844,7 +847,8 @@ __device__ __forceinline__ bool eval_at(Walker &w, Ctx &cx, int pidx, int trk, c
    return hit; }
 
 // one (parameter set, track) detector over rows [.., limit): the exact path on the samples in LDS
-__device__ __forceinline__ void walk(Walker &w, Ctx &cx, int pidx, int trk, long long limit) {
+// (literal: the burst holds an inverted -32768, which only Tile::y reads as the +32768 it is: every row through slow_step)
+__device__ __forceinline__ void walk(Walker &w, Ctx &cx, int pidx, int trk, long long limit, bool literal = false) {
    const DevCfg *cfg = cx.cfg;
    const DevParm &P = cfg->parm[pidx];
    const Tile &tl = cx.tile;
@@ -854,7 +858,7 @@ __device__ __forceinline__ void walk(Walker &w, Ctx &cx, int pidx, int trk, long
    if (w.thr_dirty) update_thresholds(w, P, cfg->lsb_per_volt);
    // ---- literal start-up path ----
    if (!w.fast) {
-      const long long fast_from = tl.reset + W + max(trk, cfg->skew[trk]) + 1;
+      const long long fast_from = literal ? 0x7fffffffffffffffll : tl.reset + W + max(trk, cfg->skew[trk]) + 1;
       while (w.next < limit && w.next < fast_from) { if (w.next >= w.start) slow_step(w, cx, pidx, trk, P, w.next); ++w.next; }
       if (w.next < fast_from) return;
       enter_fast(w, tl, trk, W, w.next); }
@@ -1150,8 +1154,8 @@ __device__ __forceinline__ void differentiate_tile(const DevCfg *cfg, const Tile
    const int spb = cfg->samples_per_bit;
    for (int i = threadIdx.x; i < nelem; i += blockDim.x) {
       const int row = i / ntrks;
-      const float v = volt(tl.x[i], mv);
-      const float vprev = (row == reset_row || i < ntrks) ? 0.0f : volt(tl.x[i - ntrks], mv);
+      const float v = volt(zc_code(tl.x[i], tl.rail), mv);
+      const float vprev = (row == reset_row || i < ntrks) ? 0.0f : volt(zc_code(tl.x[i - ntrks], tl.rail), mv);
       float delta = v - vprev;
       if (delta < 0.05f && delta > -0.05f) delta = 0;
       tl.fd[i] = delta * 0.4f * spb; } }
@@ -1408,6 +1412,32 @@ __device__ __forceinline__ void load_tile(const DevCfg *cfg, Tile &tl, const int
             v.w = (int)((((unsigned)(-(v.w << 16))) >> 16) | ((unsigned)(-(v.w >> 16)) << 16)); }
          dst[vi] = v; } } }
 
+// One lane's share of "does any sample of rows [a, b) hold the code -32768?" (under -invert that code is +32768: zc_rail): lane `lane` of `nlanes` looks
+// at every nlanes-th dword from the 4-byte boundary in front of row a (the tape is 16-byte aligned), lane 0 also at the two ends sample by sample; a and b
+// clamped to the tape.  The callers OR the lanes' answers: k_decode over its workgroup (burst_has_rail), k_rails over its wave - one scan, so that the
+// kernel that takes a burst from its chains and the kernel that walks it literally cannot disagree about which rows hold the code.
+__device__ __forceinline__ bool rail_scan_lane(const int16_t *__restrict__ rows, int ntrks, long long nrows, long long a, long long b, int lane, int nlanes) {
+   if (a < 0) a = 0;
+   if (b > nrows) b = nrows;
+   const long long e0 = a * ntrks, e1 = b * ntrks;
+   const long long d0 = (e0 + 1) & ~1ll, d1 = e1 & ~1ll;             // whole dwords [d0, d1)
+   bool hit = false;
+   if (lane == 0 && e0 < e1) hit = (e0 < d0 && rows[e0] == -32768) || (d1 >= e0 && d1 < e1 && rows[d1] == -32768);
+   if (d0 < d1) {
+      const uint32_t *q = reinterpret_cast<const uint32_t *>(rows + d0);
+      const long long nq = (d1 - d0) >> 1;
+      for (long long i = lane; i < nq; i += nlanes) { const uint32_t v = q[i]; hit |= (v & 0xffffu) == 0x8000u || (v >> 16) == 0x8000u; } }
+   return hit; }
+// ... for all lanes of a workgroup, the same answer for all
+__device__ __forceinline__ bool burst_has_rail(const int16_t *__restrict__ rows, int ntrks, long long nrows, long long a, long long b, unsigned int *lds_flag) {
+   if (threadIdx.x == 0) *lds_flag = 0;
+   __syncthreads();
+   if (rail_scan_lane(rows, ntrks, nrows, a, b, (int)threadIdx.x, (int)blockDim.x)) atomicOr(lds_flag, 1u);
+   __syncthreads();
+   const bool r = *lds_flag != 0;
+   __syncthreads();
+   return r; }
+
 // the candidate screen of every (screen, track) over the tile in LDS (with_halo: the kScreenHalo rows in front of it, too)
 __device__ __forceinline__ void run_screens(const DevCfg *cfg, const Tile &tl, bool with_halo) {
    const int hs = with_halo ? kScreenHalo / kStrip : 0;
@@ -1477,6 +1507,7 @@ __global__ void __launch_bounds__(kDecodeThreads, 2) k_decode(const DevCfg *__re
    __shared__ int s_burst;
    __shared__ long long s_min;
    __shared__ unsigned int s_flags;
+   __shared__ unsigned int s_rail;
    __shared__ int s_off[kMaxScreens * RTFE_MAXTRKS + 1];
    for (int i = threadIdx.x; i < (int)(sizeof(DevCfg) / 4); i += blockDim.x) reinterpret_cast<int *>(&cfg)[i] = reinterpret_cast<const int *>(cfgp)[i];
    __syncthreads();
@@ -1493,6 +1524,7 @@ __global__ void __launch_bounds__(kDecodeThreads, 2) k_decode(const DevCfg *__re
    cx.tile.ldw = ldw; cx.tile.halo = cfg.halo_rows; cx.tile.colof = cfg.trk_to_head;
    cx.tile.ntrks = ntrks;
    cx.tile.skew = cfg.skew;
+   cx.tile.rail = zc_rail(&cfg);
    const LdsLayout L = lds_layout(cfg);
    const bool diffpeak = cfg.differentiate && !cfg.find_zeros;     // -differentiate without -zeros: literal float detector
    cx.tile.bits = smem + L.bits;
@@ -1573,6 +1605,9 @@ __global__ void __launch_bounds__(kDecodeThreads, 2) k_decode(const DevCfg *__re
             for (int i = 0; i < 10; ++i) cx.heights[i] = 0; }
          g_first = reset / cfg.tile_rows; }
       cx.tile.reset = reset;
+      // -invert, the peak detector on the samples: an inverted -32768 is +32768, which no 16-bit lane of the screen holds - such a burst's rows all go
+      // through the literal detector (every sample it reads comes through Tile::y)
+      const bool literal = cfg.invert && !cfg.find_zeros && !diffpeak && burst_has_rail(rows, ntrks, nrows, reset, stop < hard_end ? stop : hard_end, &s_rail);
       // ---- tiles of the tape-global grid that intersect [reset, stop) ----
       const long long T = cfg.tile_rows;
       for (long long g = g_first; g * T < stop; ++g) {
@@ -1603,7 +1638,7 @@ __global__ void __launch_bounds__(kDecodeThreads, 2) k_decode(const DevCfg *__re
             Walker w = walkers[my_w];
             if (cfg.find_zeros) { if (pidx == 0 && !(zc_par && s_off[trk])) { if (cfg.differentiate) walk_diffzeros(w, cx, trk, stop); else walk_zeros(w, cx, trk, stop); } }
             else if (diffpeak) walk_diffpeak(w, cx, pidx, trk, stop);
-            else walk(w, cx, pidx, trk, stop);
+            else walk(w, cx, pidx, trk, stop, literal);
             walkers[my_w] = w; }
          if (is_walker) nrec_all[my_w] = cx.nrec;
          __syncthreads();

@@ -35,6 +35,10 @@ __global__ void __launch_bounds__(64) k_ww(const DevCfg *__restrict__ cfgp, cons
    rtfe_ww_track S = state_in[t];
    short *ring = s_ring[t];
    for (int i = 0; i < kWwRing; ++i) ring[i] = S.ring[i];
+   // -invert: v = -x reaches +32768 (the reference negates the voltage, src/readtape.c:1421) and never -32768, so the ring's 16 bits - in LDS
+   // and in the state blob - hold that one value as -32768 and every read turns it back (zc_code)
+   const int rail = zc_rail(&cfg);
+   auto rd = [&](int i) -> int { return zc_code(ring[i], rail); };
    float *heights = s_heights[t];
    for (int i = 0; i < 10; ++i) heights[i] = S.heights[i];
    Walker w = {};
@@ -55,13 +59,13 @@ __global__ void __launch_bounds__(64) k_ww(const DevCfg *__restrict__ cfgp, cons
       // ---- lookfor_peak, src/decoder.c:751-810 ----
       int old_left = 0;
       if (++right >= W) right = 0;
-      if (right == left) { old_left = ring[left]; if (++left >= W) left = 0; }
+      if (right == left) { old_left = rd(left); if (++left >= W) left = 0; }
       ring[right] = (short)v;
       if (v > maxv) maxv = v;
       if (old_left == maxv || old_left == minv) {                    // (the reference compares floats: 0.0f == volt(0), and == on volts is == on codes)
          int mx = -0x7fffffff, mn = 0x7fffffff;
          for (int ndx = left;;) {
-            const int u = ring[ndx];
+            const int u = rd(ndx);
             mx = max(mx, u); mn = min(mn, u);
             if (ndx == right) break;
             if (++ndx >= W) ndx = 0; }
@@ -74,7 +78,7 @@ __global__ void __launch_bounds__(64) k_ww(const DevCfg *__restrict__ cfgp, cons
          break; }
       const float rise = P.rise * (w.v_avg_height / 4.0f) / w.agc_gain;
       const float reqmin = P.min_peak * (w.v_avg_height / 4.0f) / w.agc_gain;
-      const float vl = volt(ring[left], mv), vr = volt(ring[right], mv);
+      const float vl = volt(rd(left), mv), vr = volt(rd(right), mv);
       const float vmax = volt(maxv, mv), vmin = volt(minv, mv);
       const bool top = vmax > vl + rise && vmax > vr + rise && (reqmin == 0 || vmax > reqmin);
       const bool bot = !top && vmin < vl - rise && vmin < vr - rise && (reqmin == 0 || vmin < -reqmin);
@@ -84,14 +88,14 @@ __global__ void __launch_bounds__(64) k_ww(const DevCfg *__restrict__ cfgp, cons
       int ld = 1, ndx = left, prev = -1;
       bool found = false;
       for (;;) {
-         if (ring[ndx] == val) { found = true; break; }
+         if (rd(ndx) == val) { found = true; break; }
          if (ndx == right) break;
          prev = ndx;
          ++ld;
          if (++ndx >= W) ndx = 0; }
       if (!found || prev < 0 || !(ld < W)) { fl |= RTFE_F_DETECTOR_FATAL; break; }         // src/decoder.c:709-710, 748
       int nxt = ndx + 1; if (nxt >= W) nxt = 0;
-      const int adjcode = refine_code(&cfg, val, ring[prev], ring[nxt], w.agc_gain, top);
+      const int adjcode = refine_code(&cfg, val, rd(prev), rd(nxt), w.agc_gain, top);
       if (nev < cap) {
          rtfe_event e;
          e.sample = (uint32_t)(n - first_row);

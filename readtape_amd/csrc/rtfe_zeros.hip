@@ -185,7 +185,7 @@ template <int NT> __global__ void __launch_bounds__(kZpThreads, RTFE_ZP_WPS) k_z
    Ctx cx;
    cx.cfg = &cfg;
    cx.row_base = row_base;
-   cx.tile.ldw = cfg.ldw; cx.tile.halo = 0; cx.tile.colof = cfg.trk_to_head; cx.tile.ntrks = ntrks; cx.tile.skew = cfg.skew;
+   cx.tile.ldw = cfg.ldw; cx.tile.halo = 0; cx.tile.colof = cfg.trk_to_head; cx.tile.ntrks = ntrks; cx.tile.skew = cfg.skew; cx.tile.rail = zc_rail(&cfg);
    cx.tile.bits = nullptr; cx.tile.bstride = 0; cx.tile.ldpos = nullptr; cx.tile.ldstride = 0; cx.tile.fd = nullptr;
    cx.heights = nullptr; cx.recs = nullptr; cx.rec_cap = 0; cx.nrec = 0;
    const int T = threadIdx.x;

@@ -273,6 +273,52 @@ def case_nrzi9_avgheight_fatal(seed=40247490):
 case_nrzi9_avgheight_fatal.parms_text = AVGHEIGHT_PARMS
 
 
+# ---- the int16 rails: what a digitiser that clips delivers.  -32768 is a sample like any other, and -invert turns it into +32768 (the reference
+# negates the voltage, src/readtape.c:1421), a code no int16 holds.  Column 0 stops at -32767: -32768 there is the TBIN end mark.
+def _clipped(t, k):
+    """the tape with its samples multiplied by k and clipped to the int16 range: every excursion a plateau on a rail"""
+    import dataclasses
+    r = np.clip(t.rows.astype(np.int64) * k, -32768, 32767)
+    r[:, 0] = np.maximum(r[:, 0], -32767)
+    return dataclasses.replace(t, rows=np.ascontiguousarray(r.astype(np.int16)))
+
+
+def case_nrzi9_rails(seed=51):
+    return _clipped(_nrzi_small(seed), 2)
+
+
+def case_gcr_rails(seed=52):
+    return _clipped(synth.gcr_tape(seed=seed, nblocks=2, minlen=40, maxlen=120, gap_samples=2500), 2)
+
+
+def case_pe_rails(seed=53):
+    return _clipped(synth.pe_tape(seed=seed, nblocks=2, minlen=30, maxlen=60, gap_samples=3000, noise_mv=3.0), 2)      # (x2 doubles the noise too: 10 mV rms would leave no group of the gaps inside PE's 49 mV quiet band)
+
+
+def case_nrzi9_rails_sparse(seed=54):
+    # an unclipped tape: every fifth bottom of heads 3 and 7 is one sample at -32768, every seventh top of head 5 one at 32767, and one
+    # bottom of head 1 a plateau of -32767 that ends in -32768 next to a 32767 (a swing of 65 535 codes between adjacent rows)
+    import dataclasses
+    t = synth.nrzi_tape(seed=seed, nblocks=3, minlen=40, maxlen=90, marks_every=0, gap_samples=1500)
+    rows = t.rows.copy()
+    ext = lambda x, s: np.flatnonzero((s * x[1:-1] > s * x[:-2]) & (s * x[1:-1] >= s * x[2:]) & (s * x[1:-1] > 5000)) + 1
+    for h in (3, 7):
+        rows[ext(rows[:, h].astype(np.int64), -1)[::5], h] = -32768
+    rows[ext(rows[:, 5].astype(np.int64), 1)[::7], 5] = 32767
+    b = ext(rows[:, 1].astype(np.int64), -1)
+    k = int(b[b.size // 2])
+    rows[k - 2:k + 1, 1] = -32767; rows[k + 1, 1] = -32768; rows[k + 2, 1] = 32767
+    return dataclasses.replace(t, rows=rows)
+
+
+def case_nrzi9_rails_skew(seed=55):
+    return _clipped(case_nrzi9_skew(seed), 2)
+
+
+def case_ww_rails(seed=56):
+    return _clipped(synth.ww_tape(seed=seed, nblocks=4, minwords=3, maxwords=10, marks_every=2, gap_samples=700), 3)
+
+
 # name -> (tape builder, reference options, oracle options); a builder's .parms_text, if any, is the NRZI/PE/GCR.parms file of the run
 CASES = {
     "nrzi9":        (case_nrzi9,      ["-nrzi"],                       []),
@@ -329,6 +375,18 @@ CASES = {
     "nrzi9_avgheight_fatal": (case_nrzi9_avgheight_fatal, ["-nrzi", "-m", "-even"],  ["-m", "-even"]),
     "gcr_errs":     (case_gcr_errors, ["-gcr"],                        []),
     "gcr_correct":  (case_gcr_errors, ["-gcr", "-correct"],            ["-correct"]),
+    "nrzi9_rails":  (case_nrzi9_rails, ["-nrzi"],                      []),
+    "nrzi9_rails_invert": (case_nrzi9_rails, ["-nrzi", "-invert"],      ["-invert"]),
+    "gcr_rails":    (case_gcr_rails,  ["-gcr"],                        []),
+    "gcr_rails_invert": (case_gcr_rails, ["-gcr", "-invert"],          ["-invert"]),
+    "pe_rails":     (case_pe_rails,   ["-pe"],                         []),
+    "pe_rails_invert": (case_pe_rails, ["-pe", "-invert"],             ["-invert"]),
+    "nrzi9_rails_sparse_invert": (case_nrzi9_rails_sparse, ["-nrzi", "-invert"], ["-invert"]),
+    "nrzi9_rails_sparse_invert_m": (case_nrzi9_rails_sparse, ["-nrzi", "-invert", "-m"], ["-invert", "-m"]),
+    "nrzi9_rails_skew_invert": (case_nrzi9_rails_skew, ["-nrzi", "-ntrks=9", "-invert", "-skew=3,1,2,0,3,0,1,2,1"], ["-invert", "-skew=3,1,2,0,3,0,1,2,1"]),
+    "nrzi9_rails_invert_diffpk": (case_nrzi9_rails, ["-nrzi", "-invert", "-differentiate"], ["-invert", "-differentiate"]),
+    "ww_rails_invert_neg": (case_ww_rails, ["-invert", "-fluxdir=neg"], ["-invert", "-fluxdir=neg"]),
+    "ww_rails_invert_pos": (case_ww_rails, ["-invert", "-fluxdir=pos"], ["-invert", "-fluxdir=pos"]),
 }
 # every reference run also gets: -v -tap -nolabels (SIMH .tap output, no IBM label handling);
 # "-nm" is added when "-m" is absent because the reference retries by default (src/readtape.c:511)

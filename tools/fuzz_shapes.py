@@ -7,6 +7,8 @@ writes such shapes over peaks of a clean NRZI tape - every sample of the window 
 
   python tools/fuzz_shapes.py [--gpu] [--e2e] [seed0 [ntapes [kind]]]     (test infrastructure: the oracle through tests/parity_util; without --gpu the kernels run on tests/cpu_emul)
   python tools/fuzz_shapes.py [--gpu] --zeros | --diffz [seed0 [ntapes]]   (-zeros / -zeros -differentiate: tests/zeros_shapes.py's tapes end to end against the oracle)
+  python tools/fuzz_shapes.py [--gpu] --rails [seed0 [ntapes]]             (the int16 rails on the amplitude detectors: tests/rail_shapes.py's tapes, every event field and the .tap
+                                                                            against the oracle; stops at the first mismatch or failure)
 """
 import os
 import sys
@@ -37,6 +39,8 @@ def main():
         make = emul_frontend
     if "--zeros" in sys.argv or "--diffz" in sys.argv:
         return zeros_main(make, gpu, seed0, ntapes, diff="--diffz" in sys.argv)
+    if "--rails" in sys.argv:
+        return rails_main(make, seed0, ntapes)
     bad = 0
     for seed in range(seed0, seed0 + ntapes):
         d = draw(seed)
@@ -96,6 +100,23 @@ def zeros_main(make, gpu, seed0, ntapes, diff):
             print("\n".join(str(x) for x in msgs[:6]), flush=True)
     print("FAILURES", bad)
     return 1 if bad else 0
+
+
+def rails_main(make, seed0, ntapes):
+    """tests/test_emul_rails.py's check of one shaped tape per seed; the first tape that fails ends the run (no retries: what failed is looked at, not run again)"""
+    import rail_shapes as rs
+    from test_emul_rails import shaped_case
+    for seed in range(seed0, seed0 + ntapes):
+        with tempfile.TemporaryDirectory() as wd:
+            try:
+                d, cov = shaped_case(make, seed, wd)
+            except Exception as e:                              # a mismatch (AssertionError) or a failure of the front end
+                print(f"FAIL seed {seed} {rs.draw(seed)}: {type(e).__name__}: {str(e)[:2000]}", flush=True)
+                print("FAILURES 1 (stopped at the first)")
+                return 1
+        print(f"ok seed {seed} {d} shapes {sum(cov.get(c, 0) for c in rs.SHAPES)} rail samples on seams {sum(cov.get(c, 0) for c in rs.SEAMS)}", flush=True)
+    print("FAILURES 0")
+    return 0
 
 
 if __name__ == "__main__":
