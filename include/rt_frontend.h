@@ -139,6 +139,17 @@ int  rtfe_create(const rtfe_config *cfg, rtfe_handle **out);
 void rtfe_destroy(rtfe_handle *h);
 int  rtfe_pkww_width(const rtfe_handle *h, int parmset);      /* src/readtape.c:1455-1457 */
 
+/* The path rtfe_scan takes for this handle, as rtfe_create decided it from the configuration and the environment knobs:
+ *   RTFE_PATH_PEAK       k_sift -> k_gain -> k_emit (NRZI peak detection)
+ *   RTFE_PATH_DENSE      k_dseg -> k_dchain (PE, GCR peak detection)
+ *   RTFE_PATH_ZEROS      k_zeros (-zeros)
+ *   RTFE_PATH_DIFFZEROS  k_diffz (-zeros -differentiate)
+ *   RTFE_PATH_SAMPLE     k_decode, a lane per (parameter set, track) on the samples: everything else, and what the knobs send there
+ *   RTFE_PATH_WW         Whirlwind: rtfe_scan refuses, rtfe_ww_scan / rtfe_ww_detector_scan serve the handle
+ * What a caller sizes its expectations by (the sample path is one to two orders of magnitude slower per row); the events do not depend on it. */
+enum { RTFE_PATH_PEAK, RTFE_PATH_DENSE, RTFE_PATH_ZEROS, RTFE_PATH_DIFFZEROS, RTFE_PATH_SAMPLE, RTFE_PATH_WW };
+int  rtfe_detector_path(const rtfe_handle *h);
+
 /* Sizes the caller must provide for a scan of nrows rows. */
 size_t  rtfe_workspace_bytes(const rtfe_handle *h, int64_t nrows);
 int64_t rtfe_max_bursts(const rtfe_handle *h, int64_t nrows);
@@ -192,7 +203,7 @@ int rtfe_find_end_mark(rtfe_handle *h, const int16_t *d_rows, int64_t nrows, int
 /* Per-kernel timing: with enable != 0, rtfe_scan records HIP events on `stream` around each of its timed spans (rtfe_kernel_name), one
  * set of events per scan in a ring of 64 sets - nothing waits, so scans queued back to back stay back to back.  rtfe_kernel_ms synchronises
  * the sets recorded since its last call and returns, per span, the elapsed milliseconds SUMMED over those scans (out[rtfe_kernel_count()]);
- * its return value is the number of scans summed (>= 0), or a negative error.  Used by bench.py. */
+ * its return value is the number of scans summed (>= 0), or a negative error.  A span a scan did not run adds exactly 0 for that scan.  Used by bench.py. */
 int rtfe_set_timing(rtfe_handle *h, int enable);
 
 /* HIP graphs (ABI 5).  enable != 0: rtfe_scan captures its launches - about twenty kernels and memsets on the caller's stream and a stream of the handle's

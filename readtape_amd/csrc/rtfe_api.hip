@@ -17,6 +17,7 @@
 #include "rtfe_sift.hip"      // single translation unit: kernels + host API
 #include "rtfe_kernels.hip"
 #include "rtfe_zeros.hip"
+#include "rtfe_diffz.hip"
 #include "rtfe_ww.hip"
 #include "rtfe_gain.hip"
 #include "rtfe_dense.hip"
@@ -44,7 +45,9 @@ struct rtfe_handle {
    int timing;
    hipEvent_t (*ev0)[12], (*ev1)[12];    // timing: a ring of kTimingRing sets of start / stop events, a set per scan (on the stream it ran on)
    int ev_next, ev_pending;             // the set the next scan records into; sets recorded since rtfe_kernel_ms last looked
+   unsigned ev_ran[64];                 // per set: the spans its scan ran (the others' events are recorded back to back and read 0, not the gap between two records)
    int zeros_kernel;                   // -zeros scans run k_zeros (RTFE_ZEROS_KERNEL=0: k_decode's zero-crossing mode, kept for tests)
+   int diffz_kernel;                   // -zeros -differentiate scans run k_diffz (RTFE_DIFFZ_KERNEL=0: k_decode's walk_diffzeros, kept for tests)
    hipStream_t side;                   // the peak path's quiet map -> bursts -> restart rows beside its lists -> streams (both only need k_sift): RTFE_OVERLAP=0 keeps them in line
    hipEvent_t ev_fork, ev_join, ev_fork2, ev_join2;
    int overlap;
@@ -142,7 +145,7 @@ extern "C" const char *rtfe_last_error(void) { return g_err; }
 //   k_sift | k_prep [k_sift_hard, k_pscan1/2, k_prep] beside k_bursts [k_qpack, k_bursts, k_zones: on a stream of the handle's own] | k_gain [the chains' heads] | k_gain_s [k_gain_seg, k_gain_join] |
 //   k_gain_tail | k_emit [k_emit_seg, k_emit, k_publish] | k_decode [the bursts the chains gave up, on the samples]
 // the sample path (PE, GCR, differentiated peaks, density detection, parameter-set sweeps with too many widths) k_quiet | k_bursts | k_decode,
-// -zeros k_quiet | k_bursts | k_zeros.  A span a scan does not run reads 0.
+// -zeros k_quiet | k_bursts | k_zeros, -zeros -differentiate k_quiet | k_bursts | k_diffz (timed in the k_zeros span).  A span a scan does not run reads 0.
 // the dense sample path (PE, GCR peak detection): k_dseg [quiet map folded in] | k_bursts [k_bursts, k_zones] | k_dchain [k_dorder, k_dchain, k_publish] | k_decode [what the chains gave up]
 static const char *KNAMES[] = {"k_quiet", "k_sift", "k_prep", "k_bursts", "k_gain", "k_gain_s", "k_gain_tail", "k_emit", "k_decode", "k_zeros", "k_dseg", "k_dchain"};
 enum { kTQuiet, kTSift, kTPrep, kTBursts, kTGain, kTGainS, kTGainTail, kTEmit, kTDecode, kTZeros, kTDseg, kTDchain };
@@ -192,7 +195,7 @@ static int create_impl(const rtfe_config *c, rtfe_handle **out, int tile_overrid
    const float bpi_s = density_mode ? 1.0f / (c->ips * ((float)c->tdelta_ns / 1e9f) * 12.0f) : c->bpi;
    rtfe_handle *h = new rtfe_handle();
    h->cfg = *c;
-   h->timing = 0; h->ev0 = nullptr; h->ev1 = nullptr; h->ev_next = 0; h->ev_pending = 0;
+   h->timing = 0; h->ev0 = nullptr; h->ev1 = nullptr; h->ev_next = 0; h->ev_pending = 0; memset(h->ev_ran, 0, sizeof h->ev_ran);
    DevCfg &d = h->dev;
    memset(&d, 0, sizeof d);
    d.mode = c->mode; d.ntrks = c->ntrks; d.invert = c->invert != 0; d.nparm = c->nparmsets;
@@ -426,6 +429,8 @@ static int create_impl(const rtfe_config *c, rtfe_handle **out, int tile_overrid
    if (hipMemcpy(h->d_dev, &d, sizeof(DevCfg), hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(h->d_dev); delete h; return fail(-22, "hipMemcpy failed"); }
    raise_dynamic_lds(reinterpret_cast<const void *>(k_decode), h->lds_bytes);
    h->zeros_kernel = getenv("RTFE_ZEROS_KERNEL") ? atoi(getenv("RTFE_ZEROS_KERNEL")) != 0 : 1;
+   h->diffz_kernel = getenv("RTFE_DIFFZ_KERNEL") ? atoi(getenv("RTFE_DIFFZ_KERNEL")) != 0 : 1;
+   if (!(d.find_zeros && d.differentiate) || d.mode == RTFE_WW) h->diffz_kernel = 0;      // (k_diffz covers every track count, -invert and every deskew delay)
    h->side = nullptr; h->overlap = getenv("RTFE_OVERLAP") ? atoi(getenv("RTFE_OVERLAP")) != 0 : 1;
    h->graphs = getenv("RTFE_GRAPHS") ? atoi(getenv("RTFE_GRAPHS")) != 0 : 0;
    memset(h->gcache, 0, sizeof h->gcache); h->gstamp = 0;
@@ -460,6 +465,7 @@ static int create_impl(const rtfe_config *c, rtfe_handle **out, int tile_overrid
    return 0; }
 
 constexpr int kTimingRing = 64;
+static_assert(kTimingRing <= 64, "rtfe_handle::ev_ran holds 64 sets");
 static void timing_free(rtfe_handle *h) {
    if (!h->ev0) return;
    for (int r = 0; r < kTimingRing; ++r) for (int i = 0; i < kNumKernels; ++i) { (void)hipEventDestroy(h->ev0[r][i]); (void)hipEventDestroy(h->ev1[r][i]); }
@@ -494,7 +500,7 @@ extern "C" int rtfe_kernel_ms(rtfe_handle *h, float *out) {
          float ms = 0;
          if (hipEventSynchronize(h->ev1[r][i]) != hipSuccess) return fail(-42, "hipEventSynchronize failed");
          if (hipEventElapsedTime(&ms, h->ev0[r][i], h->ev1[r][i]) != hipSuccess) return fail(-43, "hipEventElapsedTime failed");
-         out[i] += ms; } }
+         if ((h->ev_ran[r] >> i) & 1u) out[i] += ms; } }
    h->ev_pending = 0;
    return n; }
 
@@ -674,7 +680,7 @@ static int scan_launch(rtfe_handle *h, const int16_t *d_rows, int64_t nrows, int
    if (per_cu > wave_lim) per_cu = wave_lim;
    if (per_cu < 1) per_cu = 1;
    const int dgrid = h->num_cus * per_cu;
-   // every span's events are recorded by every scan (a span that does not run reads ~0)
+   // every span's events are recorded by every scan (a span that does not run reads 0: rtfe_kernel_ms leaves it out, ev_ran)
    bool ran[kNumKernels] = {false};
    const int evset = h->timing ? h->ev_next : 0;
    if (h->timing) { h->ev_next = (h->ev_next + 1) % kTimingRing; ++h->ev_pending; }
@@ -682,7 +688,11 @@ static int scan_launch(rtfe_handle *h, const int16_t *d_rows, int64_t nrows, int
    auto t1s = [&](int k, hipStream_t s2) { if (h->timing) (void)hipEventRecord(h->ev1[evset][k], s2); };
    auto t0 = [&](int k) { t0s(k, st); };
    auto t1 = [&](int k) { t1s(k, st); };
-   auto skip_rest = [&]() { for (int k = 0; k < kNumKernels; ++k) if (!ran[k]) { t0(k); t1(k); } };
+   auto skip_rest = [&]() {
+      unsigned mask = 0;
+      for (int k = 0; k < kNumKernels; ++k) if (ran[k]) mask |= 1u << k;
+      if (h->timing) h->ev_ran[evset] = mask;
+      for (int k = 0; k < kNumKernels; ++k) if (!ran[k]) { t0(k); t1(k); } };
    if (h->dev.peak_path) {
       // ---- the peak path: k_sift (quiet map + records) -> k_bursts -> k_zones -> k_gain -> k_emit -> k_publish -> whatever the chains gave up ----
       PeakDir *dirm = reinterpret_cast<PeakDir *>(wsb + ws_pkdir_off(h, nrows));
@@ -863,6 +873,10 @@ static int scan_launch(rtfe_handle *h, const int16_t *d_rows, int64_t nrows, int
       else if (h->dev.ntrks == 7) hipLaunchKernelGGL(k_zeros<7>, zg, zb, 0, st, (const DevCfg *)h->d_dev, d_rows, (long long)nrows, (long long)row_base, d_bursts, scratch, d_counts, d_events);
       else hipLaunchKernelGGL(k_zeros<0>, zg, zb, 0, st, (const DevCfg *)h->d_dev, d_rows, (long long)nrows, (long long)row_base, d_bursts, scratch, d_counts, d_events);
       t1(kTZeros); }
+   else if (h->diffz_kernel) {                                        // -zeros -differentiate: the transducer kernel (rtfe_diffz.hip), in the k_zeros span
+      t0(kTZeros);
+      hipLaunchKernelGGL(k_diffz, dim3(h->num_cus * 6), dim3(kDzThreads), 0, st, (const DevCfg *)h->d_dev, d_rows, (long long)nrows, (long long)row_base, d_bursts, scratch, d_counts, d_events);
+      t1(kTZeros); }
    else if (h->dev.dense_path) {                                      // PE, GCR peak detection: sub-segment lists, then a lane per chain (rtfe_dense.hip)
       const int dstop = h->dense_stop;      // (debugging: 1 = stop behind k_dseg, 2 = behind k_dchain)
       if (dstop < 2) { skip_rest(); return launch_check("rtfe_scan"); }
@@ -1029,6 +1043,15 @@ static int ww_kind(const rtfe_handle *h) {
    return h->dev.find_zeros ? (h->dev.differentiate ? RTFE_WW_DIFFZEROS : RTFE_WW_ZEROS) : (h->dev.differentiate ? RTFE_WW_DIFFPEAKS : RTFE_WW_PEAKS); }
 
 extern "C" int rtfe_ww_state_kind(const rtfe_handle *h) { return ww_kind(h); }
+// the path rtfe_scan takes for this handle, as rtfe_create decided it behind the environment knobs (scan_launch's branches in their order)
+extern "C" int rtfe_detector_path(const rtfe_handle *h) {
+   if (!h) return -1;
+   if (h->dev.mode == RTFE_WW) return RTFE_PATH_WW;
+   if (h->dev.peak_path) return RTFE_PATH_PEAK;
+   if (h->dev.find_zeros && !h->dev.differentiate && h->zeros_kernel) return RTFE_PATH_ZEROS;
+   if (h->diffz_kernel) return RTFE_PATH_DIFFZEROS;
+   if (h->dev.dense_path) return RTFE_PATH_DENSE;
+   return RTFE_PATH_SAMPLE; }
 
 extern "C" size_t rtfe_ww_state_bytes(const rtfe_handle *h) {
    const int k = ww_kind(h);

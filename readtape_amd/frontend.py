@@ -245,6 +245,8 @@ def _load_library(path=None):
     lib.rtfe_ww_scan.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     lib.rtfe_ww_state_kind.argtypes = [C.c_void_p]
+    if hasattr(lib, "rtfe_detector_path"):                 # (tools/ load older builds side by side: RTFE_LIB_PATH)
+        lib.rtfe_detector_path.argtypes = [C.c_void_p]
     lib.rtfe_ww_state_bytes.argtypes = [C.c_void_p]; lib.rtfe_ww_state_bytes.restype = C.c_size_t
     lib.rtfe_ww_detector_initial_state.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
     lib.rtfe_ww_detector_scan.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t,
@@ -351,6 +353,9 @@ class ScanResult:
         ev = np.concatenate(parts) if parts else np.zeros(0, EVENT_DTYPE)
         order = np.lexsort((ev["trk"], ev["sample"]))
         return ev[order]
+
+
+DETECTOR_PATHS = ("peak", "dense", "zeros", "diffzeros", "sample", "ww")      # RTFE_PATH_* (rt_frontend.h)
 
 
 class FrontEnd:
@@ -537,6 +542,12 @@ class FrontEnd:
 
     # --- Whirlwind: the detector's state goes in and comes back (include/rt_frontend.h: rtfe_ww_scan, rtfe_ww_detector_scan) ---
     WW_TRACK_BYTES = 224           # rtfe_ww_track: peak detection on the undifferentiated signal
+
+    @property
+    def detector_path(self) -> str:
+        """The path this handle's scans take ("peak", "dense", "zeros", "diffzeros", "sample", "ww"), as rtfe_create decided it from
+        the configuration and the environment knobs."""
+        return DETECTOR_PATHS[int(self.lib.rtfe_detector_path(self.h))]
 
     @property
     def ww_kind(self) -> int:

@@ -6,7 +6,9 @@ writes such shapes over peaks of a clean NRZI tape - every sample of the window 
 "a hair below the peak", "a little below", "well below" - and checks every event against the oracle.
 
   python tools/fuzz_shapes.py [--gpu] [--e2e] [seed0 [ntapes [kind]]]     (test infrastructure: the oracle through tests/parity_util; without --gpu the kernels run on tests/cpu_emul)
-  python tools/fuzz_shapes.py [--gpu] --zeros | --diffz [seed0 [ntapes]]   (-zeros / -zeros -differentiate: tests/zeros_shapes.py's tapes end to end against the oracle)
+  python tools/fuzz_shapes.py [--gpu] --zeros | --diffz [seed0 [ntapes]]   (-zeros / -zeros -differentiate: tests/zeros_shapes.py's tapes end to end against the oracle;
+                                                                            --diffz: tests/diffz_util.py's classes on k_diffz's seams as well, every third tape with
+                                                                            -invert, every third with a deskew delay of 50, and k_diffz against k_decode byte for byte)
   python tools/fuzz_shapes.py [--gpu] --rails [seed0 [ntapes]]             (the int16 rails on the amplitude detectors: tests/rail_shapes.py's tapes, every event field and the .tap
                                                                             against the oracle; stops at the first mismatch or failure)
 """
@@ -86,6 +88,8 @@ def zeros_main(make, gpu, seed0, ntapes, diff):
     def bursts(hdr, rows):
         return make(frontend.FrontEndConfig.from_header(hdr, find_zeros=True)).scan(rows).fetch(events=False).bursts
     bad = 0
+    if diff:
+        return diffz_main(make, gpu, seed0, ntapes)
     for seed in range(seed0, seed0 + ntapes):
         hdr, rows0, rows, sites, opts = zs.shaped(seed, bursts, diff=diff)
         if seed % 4 == 3 and not diff:
@@ -95,6 +99,48 @@ def zeros_main(make, gpu, seed0, ntapes, diff):
         cov = zs.coverage(sites, hdr, rows.shape[0], bursts(hdr, rows))
         print(f"{'ok' if not msgs else 'FAIL'} seed {seed} {zs.draw(seed)} {' '.join(opts)} sites {len(sites)} transitions {b.size} "
               f"seams {sum(cov.get(c, 0) for c in zs.SEAMS)}", flush=True)
+        if msgs:
+            bad += 1
+            print("\n".join(str(x) for x in msgs[:6]), flush=True)
+    print("FAILURES", bad)
+    return 1 if bad else 0
+
+
+def diffz_main(make, gpu, seed0, ntapes):
+    """k_diffz: a shaped tape a seed end to end against the oracle, and its scan against k_decode's (RTFE_DIFFZ_KERNEL=0) byte for byte"""
+    import diffz_util as dz
+    import zeros_shapes as zs
+    import zeros_util
+    from readtape_amd import frontend
+    if not gpu:
+        make = dz.emul_frontend
+
+    def bursts(hdr, rows, **kw):
+        return make(frontend.FrontEndConfig.from_header(hdr, find_zeros=True, **kw)).scan(rows).fetch(events=False).bursts
+    bad = 0
+    for seed in range(seed0, seed0 + ntapes):
+        hdr, rows0, rows, sites, opts = dz.shaped(seed, bursts)
+        kw = {}
+        if seed % 3 == 1:
+            opts, kw = opts + ["-invert"], {"invert": True}
+        if seed % 3 == 2:
+            opts, kw = opts + [dz.skew_opt(hdr.ntrks, seed)], {"skew": [int(x) for x in dz.skew_opt(hdr.ntrks, seed)[6:].split(",")]}
+        with tempfile.TemporaryDirectory() as wd:
+            msgs, b = zs.e2e(hdr, rows, opts, wd, None if gpu else make)
+        res = []
+        for knob in (None, "0"):
+            os.environ.pop(dz.KNOB, None)
+            if knob is not None:
+                os.environ[dz.KNOB] = knob
+            res.append(make(frontend.FrontEndConfig.from_header(hdr, find_zeros=True, differentiate=True, **kw)).scan(rows).fetch())
+        os.environ.pop(dz.KNOB, None)
+        try:
+            zeros_util.same_scan(res[1], res[0], hdr.ntrks)
+        except AssertionError as e:
+            msgs = msgs + [f"k_diffz against k_decode: {e!r}"]
+        cov = dz.coverage(sites, hdr, rows.shape[0], res[0].bursts)
+        print(f"{'ok' if not msgs else 'FAIL'} seed {seed} {zs.draw(seed)} spb {dz.spb_of(hdr)} {' '.join(opts)} sites {len(sites)} transitions {b.size} events {int(res[0].counts.sum())} "
+              + " ".join(f"{c} {cov.get(c, 0)}" for c in dz.NEW_SHAPES + dz.SEAMS), flush=True)
         if msgs:
             bad += 1
             print("\n".join(str(x) for x in msgs[:6]), flush=True)
