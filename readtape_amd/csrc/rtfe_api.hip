@@ -803,6 +803,11 @@ static int scan_launch(rtfe_handle *h, const int16_t *d_rows, int64_t nrows, int
             hipLaunchKernelGGL(k_gain_seg, dim3(h->num_cus * 16), dim3(64), 0, st, (const DevCfg *)h->d_dev, (const ChainSt *)cstp, scratch, (const CRec *)crecp, ccap, segp, (const int *)&scratch->nsegs, pk_seg_cap(h, nrows), gfirep);
             hipLaunchKernelGGL(k_gain_join, dim3(h->num_cus * 2), dim3(64), 0, st, (const DevCfg *)h->d_dev, cstp, (const rtfe_burst *)d_bursts, scratch, (const BurstCtl *)ctlp, d_counts, chainh, segp);
             t1(kTGainS); } }
+#ifdef RTFE_CPU_EMUL
+      if (getenv("RTFE_PREP_CHECK") && atoi(getenv("RTFE_PREP_CHECK")) > 1 && h->dev.pk_seg_recs > 0)
+         hipLaunchKernelGGL(k_seg_shapes, dim3(1), dim3(64), 0, st, (const DevCfg *)h->d_dev, (const ChainSt *)cstp, (const BurstScratch *)scratch, (const CRec *)crecp, ccap,
+                            (const GsSeg *)(wsb + ws_pksegs_off(h, nrows)), pk_seg_cap(h, nrows), (const float *)(wsb + ws_pkgfire_off(h, nrows)));
+#endif
       t1(kTGainTail);
       if (stop_after < 4) { skip_rest(); return launch_check("rtfe_scan"); }
       t0(kTEmit);

@@ -517,6 +517,10 @@ struct GsSeg {
    int stands, pad;
    // what k_emit_seg needs of the chain, with the entry (k_gain writes it at the hand-over): its loads of records and gains start behind ONE read, not behind a chain of three
    unsigned long long ev_index; long long reset; float h; int sl; };
+#ifdef RTFE_CPU_EMUL
+static long long g_seg_back_cross = 0, g_seg_back_any = 0;      // (emulator only: general steps of k_gain, mode 1, that walked back / across a segment's first record - k_seg_shapes prints and clears them.
+//  File scope: two handles scanning at once in one process would mix their counts; the tests that read the line scan one handle at a time)
+#endif
 __device__ __forceinline__ bool gs_same(const GsState &a, const GsState &b) {
    return __float_as_uint(a.g) == __float_as_uint(b.g) && __float_as_uint(a.vlt) == __float_as_uint(b.vlt) && __float_as_uint(a.vlb) == __float_as_uint(b.vlb)
           && a.c == b.c && a.rise_hi == b.rise_hi && a.min_lo == b.min_lo && a.min_hi == b.min_hi; }
@@ -798,6 +802,12 @@ __global__ void __launch_bounds__(64) k_gain(const DevCfg *__restrict__ cfgp, in
             if (bound + W - 2 < c) break;
             if (back >= 64) { failed = true; why = 7; return 2; }
             --i; }
+#ifdef RTFE_CPU_EMUL
+         if (mode == 1 && i < alive.i && cst[ci].nseg > 0) {                // (seg_shapes: did the walk back cross a segment's first record?)
+            const long long f0 = segs[cst[ci].seg0].first, SR = cfg.pk_seg_recs;
+            __atomic_fetch_add(&g_seg_back_any, 1ll, __ATOMIC_RELAXED);
+            if (alive.i >= f0 && (i < f0 || (alive.i - f0) / SR > (i - f0) / SR)) __atomic_fetch_add(&g_seg_back_cross, 1ll, __ATOMIC_RELAXED); }
+#endif
          if (!steady && lean && alpha_agc && w.peakcount > 15 && w.v_avg_height_count == 0) enter_steady();
          return 1; };
       // ---- mode 1 at a segment boundary: i = the next segment's first record ----
@@ -1084,6 +1094,51 @@ __global__ void __launch_bounds__(64) k_gain_join(const DevCfg *__restrict__ cfg
          counts[((size_t)b * cfg.nparm + pidx) * ntrks + trk] = nev < cap ? nev : cap;
          chain_h[(size_t)b * nwalk + wi] = cs.w.v_avg_height; }
       else cs.status = kChGeneral; } }
+#ifdef RTFE_CPU_EMUL
+// (emulator only, RTFE_PREP_CHECK > 1, behind k_gain's mode 1 - the re-joins are its work: what the segments of a scan met, counted from the finished segment
+//  table, the chains, the gains and the streams alone, for the tests that must know that their tapes reach the segments' seams.  planned: entries their chains
+//  wrote; standing: those whose events are k_emit_seg's (joined or re-joined); refused: a segment behind a standing one that ran through, not standing, its
+//  assumed state not the one its predecessor ended in (gs_same); stopped: standing segments that stopped at a record of their own; rejoined: chains whose
+//  walker adopted a segment behind a break.  nc_*: records that are not clear - without kCrClear, with kCrWeak, or with an unknown extreme (a finished stream
+//  does not say which records came from deferred candidates: prep_shapes: counts those, from the pool) - at a segment's first record, at its last, inside the
+//  warm-up stretch in front of it, within 4 records of its first.  back_any / back_cross: general steps behind the segments that walked back at all / whose
+//  walk back crossed a segment's first record.  round_edge: fired records at positions 63 | 64 of one of k_emit_seg's rounds of 64.  weak, unknown: the
+//  segments' own records with kCrWeak, with an unknown extreme.)
+__global__ void __launch_bounds__(64) k_seg_shapes(const DevCfg *__restrict__ cfgp, const ChainSt *__restrict__ cst, const BurstScratch *__restrict__ scratch, const CRec *__restrict__ crec, long long ccap,
+                                                   const GsSeg *__restrict__ segs, long long seg_cap, const float *__restrict__ gfire) {
+   if (blockIdx.x != 0 || threadIdx.x != 0) return;
+   const DevCfg &cfg = *cfgp;
+   const int nsegs = (int)min((long long)scratch->nsegs, seg_cap), S = cfg.pk_seg_recs, nwalk = cfg.nparm * cfg.ntrks;
+   const int nchains = scratch->nbursts * nwalk;
+   long long planned = 0, standing = 0, refused = 0, stopped = 0, rejoined = 0, nc_first = 0, nc_last = 0, nc_warm = 0, nc_near = 0, round_edge = 0, weak = 0, unknown = 0;
+   auto notclear = [](const CRec &r) { return !(r.w0 & kCrClear) || (r.w0 & kCrWeak) || r.w1 == 0xffff8000u; };
+   for (int si = 0; si < nsegs; ++si) {
+      const GsSeg &sg = segs[si];
+      if ((unsigned)sg.chain >= (unsigned)nchains) continue;
+      const ChainSt &cs = cst[sg.chain];
+      if (si < cs.seg0 || si >= cs.seg0 + cs.nseg || sg.sidx != si - cs.seg0 || sg.end <= sg.first) continue;
+      ++planned;
+      const CRec *r = crec + (size_t)sg.sl * ccap;
+      const long long i0 = segs[cs.seg0].first;
+      if (sg.sidx == 0) rejoined += cs.status == kChDone && cs.pad == 1;
+      else {
+         const GsSeg &pv = segs[si - 1];
+         refused += pv.stands == 1 && pv.stop == pv.end && sg.stands != 1 && !gs_same(sg.at_first, pv.at_end);
+         const int warm = cfg.parm[(sg.chain % nwalk) / cfg.ntrks].seg_warm;
+         for (long long i = sg.first - warm < i0 ? i0 : sg.first - warm; i < sg.first; ++i) nc_warm += notclear(r[i]);
+         for (long long i = sg.first - 4 < i0 ? i0 : sg.first - 4; i < sg.first + 5 && i < sg.end; ++i) nc_near += notclear(r[i]);
+         nc_first += notclear(r[sg.first]); }
+      if (si + 1 < cs.seg0 + cs.nseg) nc_last += notclear(r[sg.end - 1]);
+      for (long long i = sg.first; i < sg.end; ++i) { weak += (r[i].w0 & kCrWeak) != 0; unknown += r[i].w1 == 0xffff8000u; }
+      if (sg.stands != 1) continue;
+      ++standing;
+      stopped += sg.stop < sg.end;
+      const long long n_own = sg.stop - sg.first;
+      for (long long k = 63; k + 1 < n_own && k + 1 < S; k += 64) round_edge += (gfire[(size_t)si * S + k] != 0.0f) + (gfire[(size_t)si * S + k + 1] != 0.0f); }
+   const long long back = __atomic_exchange_n(&g_seg_back_cross, 0ll, __ATOMIC_RELAXED), back_any = __atomic_exchange_n(&g_seg_back_any, 0ll, __ATOMIC_RELAXED);
+   fprintf(stderr, "seg_shapes: recs %d planned %lld standing %lld refused %lld stopped %lld rejoined %lld nc_first %lld nc_last %lld nc_warm %lld nc_near %lld back_any %lld back_cross %lld round_edge %lld weak %lld unknown %lld\n",
+           S, planned, standing, refused, stopped, rejoined, nc_first, nc_last, nc_warm, nc_near, back_any, back, round_edge, weak, unknown); }
+#endif
 // ------------------------------------------------------------------------------------------------
 // k_emit: the events the fast path noted -> the events the reference's callbacks see.  One workgroup per chain at a time,
 // a lane per event (16 bytes in, 16 bytes out, consecutive lanes consecutive events).

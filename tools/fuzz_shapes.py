@@ -11,6 +11,9 @@ writes such shapes over peaks of a clean NRZI tape - every sample of the window 
                                                                             -invert, every third with a deskew delay of 50, and k_diffz against k_decode byte for byte)
   python tools/fuzz_shapes.py [--gpu] --rails [seed0 [ntapes]]             (the int16 rails on the amplitude detectors: tests/rail_shapes.py's tapes, every event field and the .tap
                                                                             against the oracle; stops at the first mismatch or failure)
+  python tools/fuzz_shapes.py [--gpu] --seams [seed0 [ntapes]]             (the amplitude shapes ON the seams of the peak and dense paths: tests/seam_shapes.py's tapes, every event field
+                                                                            against the oracle, two scans a handle; a line per tape with what its shapes lay across and - on the
+                                                                            emulator - what its segments met (seg_shapes:); stops at the first mismatch or failure)
 """
 import os
 import sys
@@ -43,6 +46,8 @@ def main():
         return zeros_main(make, gpu, seed0, ntapes, diff="--diffz" in sys.argv)
     if "--rails" in sys.argv:
         return rails_main(make, seed0, ntapes)
+    if "--seams" in sys.argv:
+        return seams_main(make, gpu, seed0, ntapes)
     bad = 0
     for seed in range(seed0, seed0 + ntapes):
         d = draw(seed)
@@ -162,6 +167,49 @@ def rails_main(make, seed0, ntapes):
                 return 1
         print(f"ok seed {seed} {d} shapes {sum(cov.get(c, 0) for c in rs.SHAPES)} rail samples on seams {sum(cov.get(c, 0) for c in rs.SEAMS)}", flush=True)
     print("FAILURES 0")
+    return 0
+
+
+def seams_main(make, gpu, seed0, ntapes):
+    """tests/seam_util.py's check of one shaped tape per seed (seam_tape); the first tape that fails ends the run (no retries)"""
+    import seam_shapes as ss
+    from seam_util import seam_tape
+    if not gpu:
+        os.environ["RTFE_PREP_CHECK"] = "2"
+    nfast = 0
+    for seed in range(seed0, seed0 + ntapes):
+        d = ss.draw(seed)
+        hdr, rows0, rows, sites, opts = ss.shaped(seed)
+        sys.stderr.flush()
+        with tempfile.TemporaryDirectory() as wd, tempfile.TemporaryFile() as errf:
+            keep = os.dup(2)
+            os.dup2(errf.fileno(), 2)                            # (the emulator's kernels print to the C stderr)
+            try:
+                stats, st, att = seam_tape(make, hdr, rows, opts, wd)
+                fail = None
+            except Exception as e:                               # a mismatch (AssertionError) or a failure of the front end
+                fail = f"{type(e).__name__}: {str(e)[:2000]}"
+            finally:
+                os.dup2(keep, 2)
+                os.close(keep)
+            errf.seek(0)
+            err = errf.read().decode(errors="replace")
+        if fail is None and "prep_check: stream" in err:
+            fail = "prep_check: " + err[err.index("prep_check: stream"):][:400]
+        if fail:
+            print(f"FAIL seed {seed} {d}: {fail}", flush=True)
+            print("FAILURES 1 (stopped at the first)")
+            return 1
+        cov = ss.coverage(sites, hdr)
+        peak = d["kind"].startswith("nrzi")
+        fast = (ss.fast(st) if peak else st["redone"] == 0) and stats["exact"] == 0
+        nfast += fast
+        seg, n = ss.seg_counts(err)
+        print(f"ok seed {seed} {d} rows {rows.shape[0]} sites {len(sites)} events {stats['events']} exact {stats['exact']} redone {st['redone']} "
+              + (f"lean {st['parallel']} general {st['sequential']}" if peak else f"literal_rows {st['parallel']} from_records {st['sequential']}") + f" fast {int(fast)} | "
+              + " ".join(f"{c} {cov.get(c, 0)}" for c in ss.SHAPES + (ss.PEAK_SEAMS if peak else ss.DENSE_SEAMS))
+              + (" | " + " ".join(f"{k} {v // n}" for k, v in seg.items()) if n else ""), flush=True)
+    print(f"FAILURES 0 ({nfast} of {ntapes} tapes on the fast paths)")
     return 0
 
 
