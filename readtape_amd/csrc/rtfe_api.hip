@@ -3,6 +3,7 @@
 // (src/readtape.c:1402,1455-1457; src/decoder.c:448-449) and launches the kernels of a scan.
 #include <hip/hip_runtime.h>
 
+#include <limits.h>
 #include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
@@ -55,7 +56,10 @@ struct rtfe_handle {
    int sfs_occ[kMaxScreens];           // k_sift_s: workgroups of a screen's instantiation a CU holds at once (the occupancy API, at create)
    long long work_cap;      // RTFE_WORK_CAP
    long long ccap_max;      // RTFE_CCAP (tests)
+   long long seg_cap;       // RTFE_SEG_CAP (tests: a segment table that runs full); 0: sized from the streams
    int ds_order, dchain_wgs, prep_wgs, prep_run, dense_stop, dseg_wgs, dseg_threads;      // RTFE_DS_ORDER (0: chains in burst order), RTFE_DCHAIN_WGS / RTFE_PREP_WGS / RTFE_DSEG_WGS (workgroups per CU), RTFE_PREP_RUN (tiles a wave of k_prep), RTFE_DENSE_STOP (debugging): read once, at create
+   int peak_stop, sift_wgs;                  // RTFE_PEAK_STOP (debugging: launch only the first n kernels of the peak path), RTFE_SIFT_WGS (k_sift's workgroups per CU, at most)
+   int sift_generic, sift_per_screen, dseg_generic, tile_rows_set;      // RTFE_SIFT_GENERIC / RTFE_DSEG_GENERIC (the general kernels), RTFE_SIFT_PER_SCREEN=0, RTFE_TILE_ROWS given: the kernel pickers run at create (LDS limit, occupancy) and at every scan, and must decide alike
    // rtfe_set_graphs: a scan's launches (about twenty, on two streams) captured once per set of arguments into a HIP graph and replayed - what a scan of the same
    // buffers costs the host, and the gaps between its kernels on the device, shrink to one launch
    int graphs;
@@ -121,18 +125,24 @@ static sfs_kernel_t sfs_kernel(int w, int ntrks, bool plain) {
    return ntrks == 9 ? sfs_kernel_w<9, false>(w) : (ntrks == 7 ? sfs_kernel_w<7, false>(w) : nullptr); }
 // k_dseg with the track count at compile time for the usual tapes
 typedef void (*ds_kernel_t)(const DevCfg *, const int16_t *, long long, long long, unsigned char *, unsigned char *, unsigned char *, unsigned long long *);
-static ds_kernel_t ds_kernel(int ntrks) { return getenv("RTFE_DSEG_GENERIC") ? k_dseg<0> : (ntrks == 9 ? k_dseg<9> : (ntrks == 7 ? k_dseg<7> : k_dseg<0>)); }
+static ds_kernel_t ds_kernel(const rtfe_handle *h) { return h->dseg_generic ? k_dseg<0> : (h->dev.ntrks == 9 ? k_dseg<9> : (h->dev.ntrks == 7 ? k_dseg<7> : k_dseg<0>)); }
+// k_zeros with the track count at compile time for the usual tapes
+typedef void (*zeros_kernel_t)(const DevCfg *, const int16_t *, long long, long long, rtfe_burst *, BurstScratch *, uint32_t *, rtfe_event *);
+static zeros_kernel_t zeros_kernel(int ntrks) { return ntrks == 9 ? k_zeros<9> : (ntrks == 7 ? k_zeros<7> : k_zeros<0>); }
 static int sf_wmax(const DevCfg &d) { int w = 0; for (int s = 0; s < d.nscreens; ++s) if (d.screen[s].W > w) w = d.screen[s].W; return w; }
 static int sf_threads(const DevCfg &d) { return 64 * ((d.ntrks + 1) / 2); }
 static int sf_nvec(const DevCfg &d) { return (d.pk_hl + kSfTile + d.pk_hr) * d.ntrks / 8; }
 static int sf_nv(const DevCfg &d) { return (sf_nvec(d) + sf_threads(d) - 1) / sf_threads(d); }
 // (several window widths - a parameter sweep -: a launch of the lean kernel per screen, if every screen has one: NRZI -m is three widths, 1.5 ms each where the
 //  general kernel's loop over the screens took 15.8)
-static sfs_kernel_t sf_special_sc(const DevCfg &d, int sc) { return (d.screen[sc].sure_i <= 32767 && !getenv("RTFE_SIFT_GENERIC")) ? sfs_kernel(d.screen[sc].W, d.ntrks, d.pk_plain != 0) : nullptr; }
-static sfs_kernel_t sf_special(const DevCfg &d) {
-   if (d.nscreens > 1 && getenv("RTFE_SIFT_PER_SCREEN") && atoi(getenv("RTFE_SIFT_PER_SCREEN")) == 0) return nullptr;
-   for (int sc = 0; sc < d.nscreens; ++sc) if (!sf_special_sc(d, sc)) return nullptr;
-   return d.nscreens >= 1 ? sf_special_sc(d, 0) : nullptr; }
+static sfs_kernel_t sf_special_sc(const rtfe_handle *h, int sc) {
+   const DevCfg &d = h->dev;
+   return (d.screen[sc].sure_i <= 32767 && !h->sift_generic) ? sfs_kernel(d.screen[sc].W, d.ntrks, d.pk_plain != 0) : nullptr; }
+static sfs_kernel_t sf_special(const rtfe_handle *h) {
+   const DevCfg &d = h->dev;
+   if (d.nscreens > 1 && !h->sift_per_screen) return nullptr;
+   for (int sc = 0; sc < d.nscreens; ++sc) if (!sf_special_sc(h, sc)) return nullptr;
+   return d.nscreens >= 1 ? sf_special_sc(h, 0) : nullptr; }
 // k_sift_s has a geometry of its own: a wave per pair of heads with an odd last head's tile split among them, only the window's rows in front of a tile
 static int sfs_threads(const DevCfg &d) { return 64 * sfs_waves(d.ntrks); }
 static int sfs_lds_sc(const DevCfg &d, int sc) { return (int)sfs_lds_layout(d.ntrks, d.screen[sc].W, d.pk_wave_cap, d.pk_slot).total + 64; }
@@ -155,12 +165,23 @@ extern "C" int rtfe_kernel_count(void) { return kNumKernels; }
 extern "C" const char *rtfe_kernel_name(int i) { return (i >= 0 && i < kNumKernels) ? KNAMES[i] : ""; }
 
 static int create_impl(const rtfe_config *c, rtfe_handle **out, int tile_override);
-static int sample_path_workgroups_per_cu(const rtfe_handle *h) {     // as rtfe_scan sizes k_decode's grid
+// workgroups a CU's 160 KB of LDS hold: `slack` bytes a workgroup for its static part and the allocation granularity, at most `cap` (a caller's knob and
+// the floor of one come behind it)
+static int lds_wgs_per_cu(int lds, int slack, int cap) { const int n = (160 * 1024) / (lds + slack); return n < cap ? n : cap; }
+
+// k_decode's launch.  One wave per 64 walkers: the walk phase is latency bound, so small workgroups (many resident per CU) beat wide ones; it holds
+// ~250 VGPRs => 2 waves/SIMD => 8 waves per CU.  rtfe_create's choice of the tile size, rtfe_scan's grid and rtfe_scan_exact's workgroup all come from here.
+struct DecodePlan { int walker_threads, threads, per_cu; };      // (walker_threads: rtfe_scan_exact's single workgroup, a lane per walker)
+static DecodePlan decode_plan(const rtfe_handle *h) {
+   DecodePlan p;
    const int nwalk = h->dev.nparm * h->dev.ntrks;
-   const int threads = nwalk <= 64 ? 64 : (nwalk <= 128 ? 128 : 256);
-   int per_cu = (160 * 1024) / (h->lds_bytes + 1024);
-   const int wave_lim = 8 / (threads / 64);
-   return per_cu > wave_lim ? wave_lim : (per_cu < 1 ? 1 : per_cu); }
+   p.walker_threads = p.threads = nwalk <= 64 ? 64 : (nwalk <= 128 ? 128 : 256);
+   if (h->dev.find_zeros && !h->dev.differentiate) {                 // -zeros through k_decode (rtfe_zeros.hip says when): a lane per (track, 64-row sub-segment) of the tile
+      const int lanes = h->dev.ntrks * (h->dev.tile_rows / 64);
+      while (p.threads < lanes && p.threads < 256) p.threads *= 2; }
+   p.per_cu = lds_wgs_per_cu(h->lds_bytes, 1024, 8 / (p.threads / 64));
+   if (p.per_cu < 1) p.per_cu = 1;
+   return p; }
 
 extern "C" int rtfe_create(const rtfe_config *c, rtfe_handle **out) {
    if (!c || !out) return fail(-1, "null argument");
@@ -171,10 +192,10 @@ extern "C" int rtfe_create(const rtfe_config *c, rtfe_handle **out) {
    // LDS: with 512-row tiles a sweep's workgroup can be the only one on its CU.  Shorter tiles that let more workgroups reside win
    // (C4: 98 KB -> 75 KB, one -> two per CU, +35 %); the peak path and -zeros have their own tile sizes.
    // (only then: where several workgroups already share a CU the longer tile is better - GCR, one set: 18.4 vs 22.9 ms per 5e7 rows)
-   if (!getenv("RTFE_TILE_ROWS") && !h->dev.find_zeros && h->dev.mode != RTFE_WW && sample_path_workgroups_per_cu(h) == 1) {
+   if (!h->tile_rows_set && !h->dev.find_zeros && h->dev.mode != RTFE_WW && decode_plan(h).per_cu == 1) {
       rtfe_handle *h2 = nullptr;
       if (create_impl(c, &h2, kMarginRows) == 0) {
-         if (sample_path_workgroups_per_cu(h2) > sample_path_workgroups_per_cu(h)) { rtfe_destroy(h); h = h2; }
+         if (decode_plan(h2).per_cu > decode_plan(h).per_cu) { rtfe_destroy(h); h = h2; }
          else rtfe_destroy(h2); } }
    *out = h;
    return 0; }
@@ -295,6 +316,7 @@ static int create_impl(const rtfe_config *c, rtfe_handle **out, int tile_overrid
    d.cap_frac = c->events_per_sample_cap > 0 ? c->events_per_sample_cap : 0.125f;
    {
       const char *e = getenv("RTFE_TILE_ROWS");            // tuning knob; the default is what bench.py measures
+      h->tile_rows_set = e != nullptr;
       // (-zeros in k_decode's zero-crossing mode - k_zeros does not tile -: a lane per (track, 64-row sub-segment), 14 sub-segments x 9 tracks fill two waves)
       int tr = tile_override > 0 ? tile_override : (e ? atoi(e) : ((c->find_zeros && !c->differentiate) ? 64 * (128 / (c->ntrks > 0 ? c->ntrks : 9)) : 512));
       tr = (tr / 64) * 64;
@@ -409,7 +431,7 @@ static int create_impl(const rtfe_config *c, rtfe_handle **out, int tile_overrid
    if (d.find_zeros) d.rec_cap = 8;                                   // (the zero-crossing walkers store their events at once)
    if (!d.find_zeros) {
       // k_decode is latency bound: workgroups per CU are what counts.  A smaller record buffer is taken only if it lets one more workgroup reside.
-      auto per_cu = [&](int rc) { DevCfg t = d; t.rec_cap = rc; return (160 * 1024) / ((int)lds_layout(t).total + 64 + 5500); };      // (static LDS ~ 4 KB, allocation granularity, margin)
+      auto per_cu = [&](int rc) { DevCfg t = d; t.rec_cap = rc; return lds_wgs_per_cu((int)lds_layout(t).total + 64, 5500, INT_MAX); };      // (static LDS ~ 4 KB, allocation granularity, margin)
       int best = d.rec_cap;
       for (int rc = d.rec_cap; rc >= 8; --rc) if (per_cu(rc) > per_cu(best)) best = rc;
       d.rec_cap = best; }
@@ -445,22 +467,29 @@ static int create_impl(const rtfe_config *c, rtfe_handle **out, int tile_overrid
    h->dense_stop = getenv("RTFE_DENSE_STOP") ? atoi(getenv("RTFE_DENSE_STOP")) : 99;
    h->dseg_wgs = getenv("RTFE_DSEG_WGS") ? atoi(getenv("RTFE_DSEG_WGS")) : 0;
    h->dseg_threads = getenv("RTFE_DSEG_THREADS") ? atoi(getenv("RTFE_DSEG_THREADS")) : 0;
+   h->seg_cap = getenv("RTFE_SEG_CAP") ? atoll(getenv("RTFE_SEG_CAP")) : 0;
+   h->peak_stop = getenv("RTFE_PEAK_STOP") ? atoi(getenv("RTFE_PEAK_STOP")) : 99;
+   h->sift_wgs = getenv("RTFE_SIFT_WGS") ? atoi(getenv("RTFE_SIFT_WGS")) : 0;
+   h->sift_generic = getenv("RTFE_SIFT_GENERIC") != nullptr;
+   h->sift_per_screen = !(getenv("RTFE_SIFT_PER_SCREEN") && atoi(getenv("RTFE_SIFT_PER_SCREEN")) == 0);
+   h->dseg_generic = getenv("RTFE_DSEG_GENERIC") != nullptr;
    // (k_zeros packs two tracks' 16-bit states into a lane and reads the rows where they lie: no -invert, no deskew delays, a threshold inside int16)
    if (d.invert || d.maxskew > 0 || d.ntrks < 2 || d.zc_peak_i < 1 || d.zc_peak_i > 32767 || !d.zc_parallel) h->zeros_kernel = 0;      // (RTFE_ZC_PARALLEL=0: k_decode's sequential walk, for the tests)
    if (d.peak_path) {                 // (wide rows - 16 tracks and more - do not fit k_sift's tile into LDS: peak_path is off then and the kernel is never launched)
       raise_dynamic_lds(reinterpret_cast<const void *>(sf_kernel(sf_wmax(d), sf_threads(d), sf_nv(d))), d.pk_lds);
       for (int sc = 0; sc < kMaxScreens; ++sc) h->sfs_occ[sc] = 0;
-      if (sf_special(d)) for (int sc = 0; sc < d.nscreens; ++sc) {
-         raise_dynamic_lds(reinterpret_cast<const void *>(sf_special_sc(d, sc)), sfs_lds_sc(d, sc));
+      if (sf_special(h)) for (int sc = 0; sc < d.nscreens; ++sc) {
+         raise_dynamic_lds(reinterpret_cast<const void *>(sf_special_sc(h, sc)), sfs_lds_sc(d, sc));
          int nb = 0;
-         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void *>(sf_special_sc(d, sc)), sfs_threads(d), (size_t)sfs_lds_sc(d, sc)) == hipSuccess && nb >= 1) h->sfs_occ[sc] = nb; } }
-   if (d.dense_path) raise_dynamic_lds(reinterpret_cast<const void *>(ds_kernel(d.ntrks)), (int)ds_lds_layout(d.ntrks, d.halo_rows, d.ds_pad + kDsTile + kDsRight, d.ds_up).total + 64);
+         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void *>(sf_special_sc(h, sc)), sfs_threads(d), (size_t)sfs_lds_sc(d, sc)) == hipSuccess && nb >= 1) h->sfs_occ[sc] = nb; } }
+   if (d.dense_path) raise_dynamic_lds(reinterpret_cast<const void *>(ds_kernel(h)), (int)ds_lds_layout(d.ntrks, d.halo_rows, d.ds_pad + kDsTile + kDsRight, d.ds_up).total + 64);
    (void)hipGetLastError();          // (a refused attribute must not linger as the process' "last error": the caller's runtime would report it as its own)
    if (getenv("RTFE_VERBOSE") && d.peak_path) {
       int nb = -1;
-      const int thr = sf_special(d) ? sfs_threads(d) : sf_threads(d), lds = sf_special(d) ? sfs_lds(d) : d.pk_lds;
-      (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, sf_special(d) ? reinterpret_cast<const void *>(sf_special(d)) : reinterpret_cast<const void *>(sf_kernel(sf_wmax(d), sf_threads(d), sf_nv(d))), thr, (size_t)lds);
-      fprintf(stderr, "rtfe: k_sift%s %d threads, %d bytes of LDS: %d workgroups per CU (occupancy API), %d CUs\n", sf_special(d) ? "_s" : "", thr, lds, nb, h->num_cus); }
+      const sfs_kernel_t sfs = sf_special(h);
+      const int thr = sfs ? sfs_threads(d) : sf_threads(d), lds = sfs ? sfs_lds(d) : d.pk_lds;
+      (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, sfs ? reinterpret_cast<const void *>(sfs) : reinterpret_cast<const void *>(sf_kernel(sf_wmax(d), sf_threads(d), sf_nv(d))), thr, (size_t)lds);
+      fprintf(stderr, "rtfe: k_sift%s %d threads, %d bytes of LDS: %d workgroups per CU (occupancy API), %d CUs\n", sfs ? "_s" : "", thr, lds, nb, h->num_cus); }
    *out = h;
    return 0; }
 
@@ -515,126 +544,108 @@ extern "C" void rtfe_destroy(rtfe_handle *h) {
 extern "C" int rtfe_pkww_width(const rtfe_handle *h, int parmset) {
    return (h && parmset >= 0 && parmset < h->dev.nparm) ? h->dev.parm[parmset].W : -1; }
 
-static long long nwords_for(const rtfe_handle *h, int64_t nrows) {
-   (void)h;
-   const long long nchunks = nrows / kChunkRows + 1;
-   return (nchunks + 63) / 64 + 1; }
-
-static long long ntiles_for(const rtfe_handle *h, int64_t nrows) { return (nrows + h->dev.tile_rows - 1) / h->dev.tile_rows; }
-// workspace: [0,kScratchBytes) scratch | quiet words | the zone search's counts per round | burst control blocks | the peak path's pieces
-static long long pk_tiles_for(int64_t nrows) { return (nrows + kSfTile - 1) / kSfTile; }
 constexpr int kBrRoundsMax = 1024;                                  // k_bursts_cnt / _emit: a workgroup per round of the zone search, at most this many (else one workgroup does them all)
-static size_t ws_rtot_off(const rtfe_handle *h, int64_t nrows) { return kScratchBytes + (size_t)nwords_for(h, nrows) * 8; }      // ... | the rounds' counts
-static size_t ws_ctl_off(const rtfe_handle *h, int64_t nrows) { return (ws_rtot_off(h, nrows) + (size_t)kBrRoundsMax * 4 + 255) & ~(size_t)255; }
 
 extern "C" int64_t rtfe_max_bursts(const rtfe_handle *h, int64_t nrows) {
    return (nrows / kChunkRows) / h->dev.gap_chunks + 4; }
 
-// ... | peak path: directory of the tiles' lists | per-chain baseline (k_gain -> k_emit) | record pool
-static size_t ws_pkdir_off(const rtfe_handle *h, int64_t nrows) {
-   return (ws_ctl_off(h, nrows) + (size_t)rtfe_max_bursts(h, nrows) * sizeof(BurstCtl) + 255) & ~(size_t)255; }
-static size_t pk_dir_bytes(const rtfe_handle *h, int64_t nrows) { return ((size_t)(pk_tiles_for(nrows) + 1) * h->dev.nscreens * h->dev.ntrks * sizeof(PeakDir) + 255) & ~(size_t)255; }
-static size_t pk_chain_bytes(const rtfe_handle *h, int64_t nrows) { return ((size_t)rtfe_max_bursts(h, nrows) * h->dev.nparm * h->dev.ntrks * sizeof(float) + 255) & ~(size_t)255; }
-static size_t ws_pkchain_off(const rtfe_handle *h, int64_t nrows) { return ws_pkdir_off(h, nrows) + (h->dev.peak_path ? pk_dir_bytes(h, nrows) : 0); }
-static size_t ws_pkpool_off(const rtfe_handle *h, int64_t nrows) { return ws_pkchain_off(h, nrows) + (h->dev.peak_path ? pk_chain_bytes(h, nrows) : 0); }
-static size_t pk_pool_bytes(const rtfe_handle *h, int64_t nrows) {      // one slot per (tile, screen, head)
-   if (!h->dev.peak_path) return 0;
-   return (((size_t)pk_tiles_for(nrows) * h->dev.nscreens * h->dev.ntrks * (size_t)h->dev.pk_slot) + 255) & ~(size_t)255; }
-// ... | the candidates k_sift deferred (k_sift_hard) | their overflow slots
-// (two per tile and list: a clean NRZI tape defers 0.05 % of its candidates, a noisy parameter sweep with wide windows one or two per tile and list;
-//  past the capacity a candidate becomes a "minimum unknown" record, and the chain that gets there gives up)
-static long long pk_hard_cap(const rtfe_handle *h, int64_t nrows) {
-   const long long wgs = pk_tiles_for(nrows) < (long long)h->num_cus * 8 ? pk_tiles_for(nrows) : (long long)h->num_cus * 8;      // (k_sift_s: a wave takes the list's places a chunk at a time)
-   const long long c = pk_tiles_for(nrows) * h->dev.nscreens * h->dev.ntrks * 2 + 4096 + wgs * 4 * kSfHardChunk * h->dev.nscreens;
-   return c > 0x3fffffffll ? 0x3fffffffll : c; }
-static size_t ws_pkhard_off(const rtfe_handle *h, int64_t nrows) { return ws_pkpool_off(h, nrows) + pk_pool_bytes(h, nrows); }
-static size_t ws_pkqtile_off(const rtfe_handle *h, int64_t nrows);
-static size_t ws_pkovf_off(const rtfe_handle *h, int64_t nrows) { return ws_pkhard_off(h, nrows) + (h->dev.peak_path ? (((size_t)pk_hard_cap(h, nrows) * sizeof(SfHard) + 255) & ~(size_t)255) : 0); }
-static size_t pk_ovf_bytes(const rtfe_handle *h, int64_t nrows) { return h->dev.peak_path ? (size_t)pk_hard_cap(h, nrows) * kSfOvfBytes : 0; }
-// ... | the tiles' quiet bits (k_sift -> k_qpack)
-static size_t ws_pkqtile_off(const rtfe_handle *h, int64_t nrows) { return (ws_pkovf_off(h, nrows) + pk_ovf_bytes(h, nrows) + 255) & ~(size_t)255; }
-static size_t pk_qtile_bytes(const rtfe_handle *h, int64_t nrows) { return h->dev.peak_path ? (((size_t)pk_tiles_for(nrows) * 2 + 255) & ~(size_t)255) : 0; }
-// ... | the streams' tile offsets and totals (k_pscan) | the streams (k_prep): 16-byte records, entry references
-static long long pk_hard_cap(const rtfe_handle *h, int64_t nrows);
-// (a stream's capacity: every slot's worth of records and a marker per tile.  Deferred candidates add up to three records each; a stream
-//  that outgrows the capacity through them - its slots would have to be full of records without margins as well - is not built, and its
-//  chains give up)
-static long long pk_ccap(const rtfe_handle *h, int64_t nrows) {      // (RTFE_CCAP: a smaller one, for the tests - streams that outgrow it are not built)
-   const long long c = pk_tiles_for(nrows) * (h->dev.pk_slot / 8 + 1) + 64;
-   return h->ccap_max > 0 && h->ccap_max < c ? h->ccap_max : c; }
-static size_t ws_pktstart_off(const rtfe_handle *h, int64_t nrows) { return ws_pkqtile_off(h, nrows) + pk_qtile_bytes(h, nrows); }
-static size_t pk_tstart_bytes(const rtfe_handle *h, int64_t nrows) {      // tile offsets | chunk totals | chunk offsets | stream totals
-   const size_t nl = (size_t)h->dev.nscreens * h->dev.ntrks, nch = (size_t)(pk_tiles_for(nrows) + 1023) / 1024;
-   return h->dev.peak_path ? ((((size_t)pk_tiles_for(nrows) + 2 * nch + 2) * nl * 4 + 255) & ~(size_t)255) : 0; }
-static size_t ws_pkcrec_off(const rtfe_handle *h, int64_t nrows) { return ws_pktstart_off(h, nrows) + pk_tstart_bytes(h, nrows); }
-static size_t pk_crec_bytes(const rtfe_handle *h, int64_t nrows) { return h->dev.peak_path ? (((size_t)pk_ccap(h, nrows) * h->dev.nscreens * h->dev.ntrks * sizeof(CRec) + 255) & ~(size_t)255) : 0; }
-static size_t ws_pkeref_off(const rtfe_handle *h, int64_t nrows) { return ws_pkcrec_off(h, nrows) + pk_crec_bytes(h, nrows); }
-// ... | how many records a list's deferred candidates add to (or take from) its stream (k_sift_hard -> k_pscan)
-static size_t ws_pkextra_off(const rtfe_handle *h, int64_t nrows);
-static size_t pk_extra_bytes(const rtfe_handle *h, int64_t nrows) { return h->dev.peak_path ? (((size_t)pk_tiles_for(nrows) * h->dev.nscreens * h->dev.ntrks * 4 + 255) & ~(size_t)255) : 0; }
-static size_t pk_eref_bytes(const rtfe_handle *h, int64_t nrows) { return h->dev.peak_path ? (((size_t)pk_ccap(h, nrows) * h->dev.nscreens * h->dev.ntrks * 8 + 255) & ~(size_t)255) : 0; }      // (a margin block per record, in stream order)
+// ---- the workspace of a scan: every region's offset and every capacity that depends on the row count, worked out once, in the regions' order:
+//   scratch | quiet words | rounds' counts | burst control | dir | chain | pool | hard | ovf | qtile | tstart | crec | eref | extra | cst | segs | gfire | dead | slot | total
+// (dir .. gfire: the peak path's; dead, slot: the dense path's - a region of a path the handle does not take has no bytes.  From the control blocks on every region
+//  starts on a multiple of 256 bytes.)
+struct WsLayout {
+   long long nwords, max_bursts, ptiles, dtiles;      // 64-bit words of the quiet map; bursts the table holds; tiles of k_sift (kSfTile rows) and of k_dseg (kDsTile rows)
+   long long ccap, seg_cap, work_cap; int hard_cap;   // records of a stream; segments; places of k_prep's work list; deferred candidates
+   size_t scratch, qwords, rtot, ctl, dir, chain, pool, hard, ovf, qtile, tstart, crec, eref, extra, cst, segs, gfire, work, dead, slot, total; };
 
-static size_t ws_pkextra_off(const rtfe_handle *h, int64_t nrows) { return ws_pkeref_off(h, nrows) + pk_eref_bytes(h, nrows); }
-// ... | the chains between k_gain (heads), k_gain_s (steady stretches) and k_gain (tails)
-static size_t ws_pkcst_off(const rtfe_handle *h, int64_t nrows) { return ws_pkextra_off(h, nrows) + pk_extra_bytes(h, nrows); }
-static size_t pk_cst_bytes(const rtfe_handle *h, int64_t nrows) { return h->dev.peak_path ? (((size_t)rtfe_max_bursts(h, nrows) * h->dev.nparm * h->dev.ntrks * sizeof(ChainSt) + 255) & ~(size_t)255) : 0; }
+static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
-// ... | the segments of the chains' steady stretches (k_segplan -> k_gain_seg -> k_gain_join)
-static long long pk_seg_cap(const rtfe_handle *h, int64_t nrows) {
-   if (!h->dev.peak_path) return 0;
-   if (const char *e = getenv("RTFE_SEG_CAP")) { const long long v = atoll(e); if (v >= 1) return v; }      // (tests: a table that runs full)
-   const long long S = h->dev.pk_seg_recs;
-   const long long per_stream = pk_ccap(h, nrows) / S + 1;
-   return per_stream * h->dev.nscreens * h->dev.ntrks * (h->dev.nparm < 2 ? 1 : 2) + rtfe_max_bursts(h, nrows) * h->dev.nparm * h->dev.ntrks + 64; }
-static size_t ws_pksegs_off(const rtfe_handle *h, int64_t nrows) { return ws_pkcst_off(h, nrows) + pk_cst_bytes(h, nrows); }
-static size_t pk_segs_bytes(const rtfe_handle *h, int64_t nrows) { return ((size_t)pk_seg_cap(h, nrows) * sizeof(GsSeg) + 255) & ~(size_t)255; }
+static WsLayout ws_layout(const rtfe_handle *h, int64_t nrows) {
+   const DevCfg &d = h->dev;
+   const bool pk = d.peak_path != 0, ds = d.dense_path != 0;
+   const size_t nlists = (size_t)d.nscreens * d.ntrks, nchains = (size_t)d.nparm * d.ntrks;
+   WsLayout L;
+   L.nwords = ((nrows / kChunkRows + 1) + 63) / 64 + 1;
+   L.max_bursts = rtfe_max_bursts(h, nrows);
+   L.ptiles = (nrows + kSfTile - 1) / kSfTile;
+   L.dtiles = (nrows + kDsTile - 1) / kDsTile;
+   // (a stream's capacity: every slot's worth of records and a marker per tile.  Deferred candidates add up to three records each; a stream
+   //  that outgrows the capacity through them - its slots would have to be full of records without margins as well - is not built, and its
+   //  chains give up.  RTFE_CCAP: a smaller one, for the tests)
+   L.ccap = L.ptiles * (d.pk_slot / 8 + 1) + 64;
+   if (h->ccap_max > 0 && h->ccap_max < L.ccap) L.ccap = h->ccap_max;
+   // (two deferred candidates per tile and list: a clean NRZI tape defers 0.05 % of its candidates, a noisy parameter sweep with wide windows one or two per tile and list;
+   //  past the capacity a candidate becomes a "minimum unknown" record, and the chain that gets there gives up.  k_sift_s: a wave takes the list's places a chunk at a time)
+   const long long sift_wgs = L.ptiles < (long long)h->num_cus * 8 ? L.ptiles : (long long)h->num_cus * 8;
+   const long long hard = L.ptiles * d.nscreens * d.ntrks * 2 + 4096 + sift_wgs * 4 * kSfHardChunk * d.nscreens;
+   L.hard_cap = (int)(hard > 0x3fffffffll ? 0x3fffffffll : hard);
+   L.seg_cap = 0;
+   if (pk) L.seg_cap = h->seg_cap >= 1 ? h->seg_cap
+                                       : (L.ccap / d.pk_seg_recs + 1) * d.nscreens * d.ntrks * (d.nparm < 2 ? 1 : 2) + L.max_bursts * d.nparm * d.ntrks + 64;
+   // the regions in order: one that is `on` starts at the cursor and moves it to the next multiple of 256 bytes behind its end
+   size_t off = 0;
+   auto take = [&off](bool on, size_t bytes) { const size_t at = off; if (on) off = align256(off + bytes); return at; };
+   L.scratch = 0;                                                                  // the BurstScratch block
+   L.qwords = kScratchBytes;                                                       // the quiet map, a bit per 64 rows (not padded: the counts follow at once)
+   L.rtot = L.qwords + (size_t)L.nwords * 8;                                       // the zone search's counts per round
+   off = align256(L.rtot + (size_t)kBrRoundsMax * 4);
+   L.ctl = take(true, (size_t)L.max_bursts * sizeof(BurstCtl));                    // burst control blocks
+   L.dir = take(pk, (size_t)(L.ptiles + 1) * nlists * sizeof(PeakDir));            // directory of the tiles' lists
+   L.chain = take(pk, (size_t)L.max_bursts * nchains * sizeof(float));             // per-chain baseline (k_gain -> k_emit)
+   L.pool = take(pk, (size_t)L.ptiles * nlists * (size_t)d.pk_slot);               // record pool: one slot per (tile, screen, head)
+   L.hard = take(pk, (size_t)L.hard_cap * sizeof(SfHard));                         // the candidates k_sift deferred (k_sift_hard)
+   L.ovf = take(pk, (size_t)L.hard_cap * kSfOvfBytes);                             // their overflow slots
+   L.qtile = take(pk, (size_t)L.ptiles * 2);                                       // the tiles' quiet bits (k_sift -> k_qpack)
+   L.tstart = take(pk, ((size_t)L.ptiles + 2 * ((size_t)(L.ptiles + 1023) / 1024) + 2) * nlists * 4);      // the streams' tile offsets | chunk totals | chunk offsets | stream totals (k_pscan)
+   L.crec = take(pk, (size_t)L.ccap * nlists * sizeof(CRec));                      // the streams (k_prep): 16-byte records
+   L.eref = take(pk, (size_t)L.ccap * nlists * 8);                                 // a margin block per record, in stream order
+   L.extra = take(pk, (size_t)L.ptiles * nlists * 4);                              // how many records a list's deferred candidates add to (or take from) its stream (k_sift_hard -> k_pscan)
+   L.cst = take(pk, (size_t)L.max_bursts * nchains * sizeof(ChainSt));             // the chains between k_gain (heads), k_gain_s (steady stretches) and k_gain (tails)
+   L.segs = take(pk, (size_t)L.seg_cap * sizeof(GsSeg));                           // the segments of the chains' steady stretches (k_segplan -> k_gain_seg -> k_gain_join)
+   L.gfire = take(pk, (size_t)L.seg_cap * (size_t)(d.pk_seg_recs > 0 ? d.pk_seg_recs : 0) * 4);      // per record of a segment: the gain in force if it fired (k_gain_seg -> k_emit_seg)
+   // k_prep's work list for k_clear lives in the gains' region - nothing reads it behind k_clear; 8 bytes a place, counted in an int
+   // (RTFE_WORK_CAP, tests: a list that runs full - what does not fit stays unmarked, the general step's)
+   L.work = L.gfire;
+   L.work_cap = (long long)((off - L.gfire) / 8);
+   if (h->work_cap >= 0 && h->work_cap < L.work_cap) L.work_cap = h->work_cap;
+   if (L.work_cap > 0x7ffffe00ll) L.work_cap = 0x7ffffe00ll;
+   L.dead = take(ds, (size_t)L.dtiles * d.nscreens);                               // the dense path: per (tile, width) "nothing above the screen"
+   L.slot = take(ds, (size_t)L.dtiles * kDsJ * d.nuset * d.ntrks * (size_t)d.ds_slot + 256);      // the sub-segments' slots, the bands in their headers (+ a slot's worth: k_dchain reads nine 16-byte units of the last slot)
+   L.total = off + 256;
+   return L; }
 
-// ... | per record of a segment: the gain in force if it fired (k_gain_seg -> k_emit_seg)
-static size_t ws_pkgfire_off(const rtfe_handle *h, int64_t nrows) { return ws_pksegs_off(h, nrows) + pk_segs_bytes(h, nrows); }
-static size_t pk_gfire_bytes(const rtfe_handle *h, int64_t nrows) { return ((size_t)pk_seg_cap(h, nrows) * (size_t)(h->dev.pk_seg_recs > 0 ? h->dev.pk_seg_recs : 0) * 4 + 255) & ~(size_t)255; }
-
-// (k_prep's work list for k_clear lives in the gains' region - nothing reads it behind k_clear; 8 bytes a place, counted in an int)
-static long long pk_work_cap(const rtfe_handle *h, int64_t nrows) {
-   long long c = (long long)(pk_gfire_bytes(h, nrows) / 8);
-   if (h->work_cap >= 0 && h->work_cap < c) c = h->work_cap;      // (RTFE_WORK_CAP, tests: a list that runs full - what does not fit stays unmarked, the general step's)
-   return c > 0x7ffffe00ll ? 0x7ffffe00ll : c; }
-
-// ... | the dense sample path: per (tile, width) "nothing above the screen" | per (sub-segment, track) the band | the slots
-static long long ds_tiles_for(int64_t nrows) { return (nrows + kDsTile - 1) / kDsTile; }
-static size_t ws_dsdead_off(const rtfe_handle *h, int64_t nrows) { return (ws_pkgfire_off(h, nrows) + pk_gfire_bytes(h, nrows) + 255) & ~(size_t)255; }
-static size_t ds_dead_bytes(const rtfe_handle *h, int64_t nrows) { return h->dev.dense_path ? (((size_t)ds_tiles_for(nrows) * h->dev.nscreens + 255) & ~(size_t)255) : 0; }
-static size_t ws_dsband_off(const rtfe_handle *h, int64_t nrows) { return ws_dsdead_off(h, nrows) + ds_dead_bytes(h, nrows); }
-static size_t ds_band_bytes(const rtfe_handle *h, int64_t nrows) { (void)h; (void)nrows; return 0; }      // (the bands travel in the slots' headers: the region of their own is gone - ADVICE r4)
-static size_t ws_dsslot_off(const rtfe_handle *h, int64_t nrows) { return ws_dsband_off(h, nrows) + ds_band_bytes(h, nrows); }
-static size_t ds_slot_bytes(const rtfe_handle *h, int64_t nrows) { return h->dev.dense_path ? (((size_t)ds_tiles_for(nrows) * kDsJ * h->dev.nuset * h->dev.ntrks * (size_t)h->dev.ds_slot + 511) & ~(size_t)255) : 0; }      // (+ a slot's worth: k_dchain reads nine 16-byte units of the last slot)
-
-extern "C" size_t rtfe_workspace_bytes(const rtfe_handle *h, int64_t nrows) {
-   return ws_dsslot_off(h, nrows) + ds_slot_bytes(h, nrows) + 256; }
+extern "C" size_t rtfe_workspace_bytes(const rtfe_handle *h, int64_t nrows) { return ws_layout(h, nrows).total; }
 
 extern "C" int64_t rtfe_event_capacity(const rtfe_handle *h, int64_t nrows) {
    const double per_track = (double)nrows * h->dev.cap_frac + 128.0 * (double)rtfe_max_bursts(h, nrows) + (double)kMarginRows;
    return (int64_t)(per_track * h->dev.nparm * h->dev.ntrks) + 4096; }
 
+// the regions as the kernels take them
+struct WsView {
+   BurstScratch *scratch; unsigned long long *qwords; uint32_t *rtot; BurstCtl *ctl;
+   PeakDir *dir; float *chain; unsigned char *pool; SfHard *hard; unsigned char *ovf; uint16_t *qtile;
+   uint32_t *tstart, *ctotc, *coff, *ctot;      // the tstart region: tile offsets | chunk totals | chunk offsets | stream totals
+   CRec *crec; uint2 *eref; int *extra; ChainSt *cst; GsSeg *segs; float *gfire; unsigned long long *work;
+   unsigned char *dead, *slot; };
+
+template <class T> static T *ws_at(void *ws, size_t off) { return reinterpret_cast<T *>(static_cast<char *>(ws) + off); }
+
+static WsView ws_view(const rtfe_handle *h, const WsLayout &L, void *ws) {
+   WsView w;
+   w.scratch = ws_at<BurstScratch>(ws, L.scratch); w.qwords = ws_at<unsigned long long>(ws, L.qwords); w.rtot = ws_at<uint32_t>(ws, L.rtot); w.ctl = ws_at<BurstCtl>(ws, L.ctl);
+   w.dir = ws_at<PeakDir>(ws, L.dir); w.chain = ws_at<float>(ws, L.chain); w.pool = ws_at<unsigned char>(ws, L.pool); w.hard = ws_at<SfHard>(ws, L.hard);
+   w.ovf = ws_at<unsigned char>(ws, L.ovf); w.qtile = ws_at<uint16_t>(ws, L.qtile);
+   const size_t nlists = h->dev.peak_path ? (size_t)h->dev.nscreens * h->dev.ntrks : 0, nsc = (size_t)(L.ptiles + 1023) / 1024;      // chunks of 1024 tiles (k_pscan)
+   w.tstart = ws_at<uint32_t>(ws, L.tstart); w.ctotc = w.tstart + (size_t)L.ptiles * nlists; w.coff = w.ctotc + nsc * nlists; w.ctot = w.coff + nsc * nlists;
+   w.crec = ws_at<CRec>(ws, L.crec); w.eref = ws_at<uint2>(ws, L.eref); w.extra = ws_at<int>(ws, L.extra); w.cst = ws_at<ChainSt>(ws, L.cst);
+   w.segs = ws_at<GsSeg>(ws, L.segs); w.gfire = ws_at<float>(ws, L.gfire); w.work = ws_at<unsigned long long>(ws, L.work);
+   w.dead = ws_at<unsigned char>(ws, L.dead); w.slot = ws_at<unsigned char>(ws, L.slot);
+   return w; }
+
 static int launch_check(const char *what) {
    hipError_t e = hipGetLastError();
    if (e != hipSuccess) return fail(-30, "%s: %s", what, hipGetErrorString(e));
    return 0; }
-
-// quiet map -> burst table.  Long maps: a workgroup per round of 2^24 rows in two passes and a tail (k_bursts_cnt / _emit / _tail); short ones
-// (or absurdly long ones): the single workgroup that does the rounds in turn.  RTFE_BURSTS_WPR: words per round (tests: many rounds on a short tape).
-static void launch_bursts(const rtfe_handle *h, hipStream_t s, const unsigned long long *qwords, long long nwords, long long nchunks, int64_t nrows, int64_t own_rows,
-                          int first_is_tape_start, int64_t event_capacity, rtfe_burst *d_bursts, long long maxb, BurstScratch *scratch, int32_t *d_nbursts, uint32_t *rtot) {
-   const int wpr_env = h->bursts_wpr;
-   const int wpr = (wpr_env >= 1 && wpr_env <= kBrWords) ? wpr_env : kBrWords;
-   const long long rounds = (nwords + wpr - 1) / wpr;
-   if ((wpr_env > 0 || rounds >= 3) && rounds <= kBrRoundsMax && h->dev.debug != 5) {
-      hipLaunchKernelGGL(k_bursts_cnt, dim3((unsigned)rounds), dim3(1024), 0, s, qwords, nwords, nchunks, wpr, h->dev.gap_chunks, first_is_tape_start, maxb, rtot);
-      hipLaunchKernelGGL(k_bursts_emit, dim3((unsigned)rounds), dim3(1024), 0, s, qwords, nwords, nchunks, (long long)nrows, wpr, h->dev.gap_chunks, first_is_tape_start, d_bursts, maxb, (const uint32_t *)rtot);
-      hipLaunchKernelGGL(k_bursts_tail, dim3(1), dim3(1024), 0, s, (int)rounds, (const uint32_t *)rtot, (long long)nrows, (long long)own_rows, h->dev.ntrks, h->dev.gap_chunks,
-                         h->dev.cap_frac, h->dev.nparm, (long long)event_capacity, d_bursts, maxb, scratch, d_nbursts); }
-   else
-      hipLaunchKernelGGL(k_bursts, dim3(1), dim3(1024), 0, s, qwords, nwords, nchunks, (long long)nrows, (long long)own_rows, h->dev.ntrks,
-                         h->dev.gap_chunks, first_is_tape_start, h->dev.cap_frac, h->dev.nparm, (long long)event_capacity, d_bursts, maxb, scratch, d_nbursts, h->dev.debug == 5 ? 1 : 0); }
 
 // the handle's side stream (made at the first scan that wants it - outside any stream capture)
 static void ensure_side(rtfe_handle *h) {
@@ -647,94 +658,155 @@ static void ensure_side(rtfe_handle *h) {
    else { (void)hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming); (void)hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming);
           (void)hipEventCreateWithFlags(&h->ev_fork2, hipEventDisableTiming); (void)hipEventCreateWithFlags(&h->ev_join2, hipEventDisableTiming); } }
 
-static int scan_launch(rtfe_handle *h, const int16_t *d_rows, int64_t nrows, int64_t own_rows, int64_t row_base, int first_is_tape_start,
-                       void *d_workspace, size_t workspace_bytes,
-                       rtfe_burst *d_bursts, int64_t max_bursts, int32_t *d_nbursts,
-                       uint32_t *d_counts, rtfe_event *d_events, int64_t event_capacity, void *stream) {
-   if (!h || !d_rows || !d_workspace || !d_bursts || !d_nbursts || !d_counts || !d_events) return fail(-1, "null argument");
-   if (h->dev.mode == RTFE_WW) return fail(-44, "Whirlwind tapes have no independent bursts: use rtfe_ww_scan");
-   if (((uintptr_t)d_rows & 15) != 0) return fail(-31, "d_rows must be 16-byte aligned");
-   if (workspace_bytes < rtfe_workspace_bytes(h, nrows)) return fail(-32, "workspace too small");
-   // the peak path addresses rows with 32 bits and a record's margin entries by a 32-bit index (2-byte units) into pool + overflow slots
-   if (h->dev.peak_path && (nrows >= 0x7ff00000ll || (ws_pkqtile_off(h, nrows) - ws_pkpool_off(h, nrows)) / 2 >= 0xffffffffull))
-      return fail(-36, "%lld rows are too many for one rtfe_scan on the peak path: scan the tape in fragments (own_rows)", (long long)nrows);
-   if (nrows <= 0 || max_bursts < 1) return fail(-33, "nothing to scan");
-   if (own_rows <= 0 || own_rows > nrows) return fail(-35, "own_rows must be in (0, nrows]");
-   hipStream_t st = (hipStream_t)stream;
-   const long long nchunks = nrows / kChunkRows;                      // complete groups of 64 rows
-   const long long nwords = nwords_for(h, nrows);
-   BurstScratch *scratch = reinterpret_cast<BurstScratch *>(d_workspace);
-   unsigned long long *qwords = reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(d_workspace) + kScratchBytes);
-   int grid = (int)(nwords < (long long)h->num_cus * 8 ? nwords : (long long)h->num_cus * 8);
-   BurstCtl *ctlp = reinterpret_cast<BurstCtl *>(reinterpret_cast<char *>(d_workspace) + ws_ctl_off(h, nrows));
-   char *wsb = reinterpret_cast<char *>(d_workspace);
-   // one wave per 64 walkers: k_decode's walk phase is latency bound, so small workgroups (many resident per CU)
-   // beat wide ones; it holds ~250 VGPRs => 2 waves/SIMD => 8 waves per CU
-   const int nwalk = h->dev.nparm * h->dev.ntrks;
-   int threads = nwalk <= 64 ? 64 : (nwalk <= 128 ? 128 : 256);
-   if (h->dev.find_zeros && !h->dev.differentiate) {                 // -zeros through k_decode (rtfe_zeros.hip says when): a lane per (track, 64-row sub-segment) of the tile
-      const int lanes = h->dev.ntrks * (h->dev.tile_rows / 64);
-      while (threads < lanes && threads < 256) threads *= 2; }
-   int per_cu = (160 * 1024) / (h->lds_bytes + 1024);
-   const int wave_lim = 8 / (threads / 64);
-   if (per_cu > wave_lim) per_cu = wave_lim;
-   if (per_cu < 1) per_cu = 1;
-   const int dgrid = h->num_cus * per_cu;
+// rtfe_scan's arguments
+struct ScanArgs {
+   const int16_t *d_rows; int64_t nrows, own_rows, row_base; int first_is_tape_start;
+   void *d_workspace; size_t workspace_bytes;
+   rtfe_burst *d_bursts; int64_t max_bursts; int32_t *d_nbursts;
+   uint32_t *d_counts; rtfe_event *d_events; int64_t event_capacity; void *stream; };
+
+// what a captured graph of a scan is good for: every argument but the stream
+static void graph_key(const ScanArgs &a, unsigned long long key[13]) {
+   auto u = [](auto v) { return (unsigned long long)(uintptr_t)v; };
+   const unsigned long long k[13] = {u(a.d_rows), u(a.nrows), u(a.own_rows), u(a.row_base), u(a.first_is_tape_start), u(a.d_workspace), u(a.workspace_bytes),
+                                     u(a.d_bursts), u(a.max_bursts), u(a.d_nbursts), u(a.d_counts), u(a.d_events), u(a.event_capacity)};
+   memcpy(key, k, sizeof k); }
+
+// One scan's launches: what the three paths share, and the paths.
+struct Scan {
+   rtfe_handle *h; const DevCfg &d; const ScanArgs &a; hipStream_t st; WsLayout L; WsView w;
+   long long nrows, row_base, nchunks, maxb;      // (nchunks: complete groups of 64 rows; maxb: bursts the caller's table and the workspace both hold)
    // every span's events are recorded by every scan (a span that does not run reads 0: rtfe_kernel_ms leaves it out, ev_ran)
-   bool ran[kNumKernels] = {false};
-   const int evset = h->timing ? h->ev_next : 0;
-   if (h->timing) { h->ev_next = (h->ev_next + 1) % kTimingRing; ++h->ev_pending; }
-   auto t0s = [&](int k, hipStream_t s2) { ran[k] = true; if (h->timing) (void)hipEventRecord(h->ev0[evset][k], s2); };
-   auto t1s = [&](int k, hipStream_t s2) { if (h->timing) (void)hipEventRecord(h->ev1[evset][k], s2); };
-   auto t0 = [&](int k) { t0s(k, st); };
-   auto t1 = [&](int k) { t1s(k, st); };
-   auto skip_rest = [&]() {
+   int evset; bool ran[kNumKernels];
+   void t0s(int k, hipStream_t s) { ran[k] = true; if (h->timing) (void)hipEventRecord(h->ev0[evset][k], s); }
+   void t1s(int k, hipStream_t s) { if (h->timing) (void)hipEventRecord(h->ev1[evset][k], s); }
+   void t0(int k) { t0s(k, st); }
+   void t1(int k) { t1s(k, st); }
+   void skip_rest() {
       unsigned mask = 0;
       for (int k = 0; k < kNumKernels; ++k) if (ran[k]) mask |= 1u << k;
       if (h->timing) h->ev_ran[evset] = mask;
-      for (int k = 0; k < kNumKernels; ++k) if (!ran[k]) { t0(k); t1(k); } };
-   if (h->dev.peak_path) {
-      // ---- the peak path: k_sift (quiet map + records) -> k_bursts -> k_zones -> k_gain -> k_emit -> k_publish -> whatever the chains gave up ----
-      PeakDir *dirm = reinterpret_cast<PeakDir *>(wsb + ws_pkdir_off(h, nrows));
-      float *chainh = reinterpret_cast<float *>(wsb + ws_pkchain_off(h, nrows));
-      unsigned char *pkpool = reinterpret_cast<unsigned char *>(wsb + ws_pkpool_off(h, nrows));
-      SfHard *hardp = reinterpret_cast<SfHard *>(wsb + ws_pkhard_off(h, nrows));
-      unsigned char *ovfp = reinterpret_cast<unsigned char *>(wsb + ws_pkovf_off(h, nrows));
-      const int hard_cap = (int)pk_hard_cap(h, nrows);
-      const long long ptiles = pk_tiles_for(nrows);
-      // the scratch block and the deferred candidates' counts cleared, and - a handle's first scan - the screen's floor estimated from the samples (k_scan_begin)
-      hipLaunchKernelGGL(k_scan_begin, dim3(h->num_cus * 4), dim3(256), 0, st, h->d_dev, scratch, reinterpret_cast<uint4 *>(wsb + ws_pkextra_off(h, nrows)), (long long)(pk_extra_bytes(h, nrows) / 16), d_rows, (long long)nrows);
-      const int stop_after = getenv("RTFE_PEAK_STOP") ? atoi(getenv("RTFE_PEAK_STOP")) : 99;      // (debugging: launch only the first n kernels of the path)
+      for (int k = 0; k < kNumKernels; ++k) if (!ran[k]) { t0(k); t1(k); } }
+   // quiet map -> burst table.  Long maps: a workgroup per round of 2^24 rows in two passes and a tail (k_bursts_cnt / _emit / _tail); short ones
+   // (or absurdly long ones): the single workgroup that does the rounds in turn.  RTFE_BURSTS_WPR: words per round (tests: many rounds on a short tape).
+   void launch_bursts(hipStream_t s) {
+      const int wpr_env = h->bursts_wpr;
+      const int wpr = (wpr_env >= 1 && wpr_env <= kBrWords) ? wpr_env : kBrWords;
+      const long long rounds = (L.nwords + wpr - 1) / wpr;
+      if ((wpr_env > 0 || rounds >= 3) && rounds <= kBrRoundsMax && d.debug != 5) {
+         hipLaunchKernelGGL(k_bursts_cnt, dim3((unsigned)rounds), dim3(1024), 0, s, (const unsigned long long *)w.qwords, L.nwords, nchunks, wpr, d.gap_chunks, a.first_is_tape_start, maxb, w.rtot);
+         hipLaunchKernelGGL(k_bursts_emit, dim3((unsigned)rounds), dim3(1024), 0, s, (const unsigned long long *)w.qwords, L.nwords, nchunks, nrows, wpr, d.gap_chunks, a.first_is_tape_start, a.d_bursts, maxb, (const uint32_t *)w.rtot);
+         hipLaunchKernelGGL(k_bursts_tail, dim3(1), dim3(1024), 0, s, (int)rounds, (const uint32_t *)w.rtot, nrows, (long long)a.own_rows, d.ntrks, d.gap_chunks,
+                            d.cap_frac, d.nparm, (long long)a.event_capacity, a.d_bursts, maxb, w.scratch, a.d_nbursts); }
+      else
+         hipLaunchKernelGGL(k_bursts, dim3(1), dim3(1024), 0, s, (const unsigned long long *)w.qwords, L.nwords, nchunks, nrows, (long long)a.own_rows, d.ntrks,
+                            d.gap_chunks, a.first_is_tape_start, d.cap_frac, d.nparm, (long long)a.event_capacity, a.d_bursts, maxb, w.scratch, a.d_nbursts, d.debug == 5 ? 1 : 0); }
+   // the restart rows of all bursts (rtfe_gain.hip)
+   void launch_zones(hipStream_t s) {
+      hipLaunchKernelGGL(k_zones, dim3(h->num_cus * 8), dim3(64), 0, s, h->d_dev, a.d_rows, nrows, (const rtfe_burst *)a.d_bursts, (const BurstScratch *)w.scratch, w.ctl);
+      if (d.invert)      // (an inverted -32768 is +32768, wider than a record: bursts that hold one go to the sample path's literal walk)
+         hipLaunchKernelGGL(k_rails, dim3(h->num_cus * 8), dim3(64), 0, s, h->d_dev, a.d_rows, nrows, (const rtfe_burst *)a.d_bursts, (const BurstScratch *)w.scratch, w.ctl); }
+   // kDecodeAll: every burst in one pass over its samples; kDecodeRedo: the bursts the peak path's or the dense path's chains gave up
+   void launch_decode(int mode) {
+      const DecodePlan dp = decode_plan(h);
+      t0(kTDecode);
+      hipLaunchKernelGGL(k_decode, dim3(h->num_cus * dp.per_cu), dim3(dp.threads), h->lds_bytes, st, h->d_dev, a.d_rows, nrows,
+                         row_base, a.d_bursts, w.scratch, a.d_counts, a.d_events, 0xffffffffu, 0, 0, mode, w.ctl);
+      t1(kTDecode); }
+   // k_sift: the quiet bits and the lists of every tile
+   void launch_sift() {
       t0(kTSift);
-      const sfs_kernel_t sfs = sf_special(h->dev);
-      const int pthreads = sfs ? sfs_threads(h->dev) : sf_threads(h->dev), plds = sfs ? sfs_lds(h->dev) : h->dev.pk_lds;
-      int spc = (160 * 1024) / (plds + 512);
-      if (spc * (pthreads / 64) > 32) spc = 32 / (pthreads / 64);
-      if (const char *e = getenv("RTFE_SIFT_WGS")) { const int v = atoi(e); if (v >= 1 && v < spc) spc = v; }
+      const sfs_kernel_t sfs = sf_special(h);
+      const int pthreads = sfs ? sfs_threads(d) : sf_threads(d), plds = sfs ? sfs_lds(d) : d.pk_lds;
+      int spc = lds_wgs_per_cu(plds, 512, 32 / (pthreads / 64));
+      if (h->sift_wgs >= 1 && h->sift_wgs < spc) spc = h->sift_wgs;
       if (spc < 1) spc = 1;
       long long pgrid = (long long)h->num_cus * spc;
-      if (pgrid > ptiles) pgrid = ptiles;
-      uint16_t *qtile = reinterpret_cast<uint16_t *>(wsb + ws_pkqtile_off(h, nrows));
+      if (pgrid > L.ptiles) pgrid = L.ptiles;
       if (sfs) {
-         for (int sc = 0; sc < h->dev.nscreens; ++sc) {
-            SfArgs a;
-            a.rows = d_rows; a.nrows = nrows; a.ntiles = (int)ptiles; a.qtile = sc == 0 ? qtile : nullptr; a.dir = dirm; a.pool = pkpool; a.hard = hardp; a.hard_cap = hard_cap;
-            a.hard_count = &scratch->hard_count; a.dbg = scratch->scr; a.hcap = h->dev.pk_slot; a.wave_cap = h->dev.pk_wave_cap; a.invert = h->dev.invert;
-            a.quiet_i = h->dev.quiet_i; a.cfg = h->d_dev; a.hi_i = h->dev.screen[sc].sure_i;
-            a.cut = h->dev.cut; a.debug = h->dev.debug; a.defer = 1; a.nscreens = h->dev.nscreens; a.sc = sc;
-            const int lds_sc = sfs_lds_sc(h->dev, sc);
-            int spc_sc = (160 * 1024) / (lds_sc + 512);
-            if (spc_sc > spc) spc_sc = spc;
+         for (int sc = 0; sc < d.nscreens; ++sc) {
+            SfArgs sa;
+            sa.rows = a.d_rows; sa.nrows = nrows; sa.ntiles = (int)L.ptiles; sa.qtile = sc == 0 ? w.qtile : nullptr; sa.dir = w.dir; sa.pool = w.pool; sa.hard = w.hard; sa.hard_cap = L.hard_cap;
+            sa.hard_count = &w.scratch->hard_count; sa.dbg = w.scratch->scr; sa.hcap = d.pk_slot; sa.wave_cap = d.pk_wave_cap; sa.invert = d.invert;
+            sa.quiet_i = d.quiet_i; sa.cfg = h->d_dev; sa.hi_i = d.screen[sc].sure_i;
+            sa.cut = d.cut; sa.debug = d.debug; sa.defer = 1; sa.nscreens = d.nscreens; sa.sc = sc;
+            const int lds_sc = sfs_lds_sc(d, sc);
+            int spc_sc = lds_wgs_per_cu(lds_sc, 512, spc);
             if (h->sfs_occ[sc] >= 1 && spc_sc > h->sfs_occ[sc]) spc_sc = h->sfs_occ[sc];      // (persistent workgroups: never more than are resident at once - the registers may allow fewer than the LDS)
             if (spc_sc < 1) spc_sc = 1;
             long long grid_sc = (long long)h->num_cus * spc_sc;
-            if (grid_sc > ptiles) grid_sc = ptiles;
-            hipLaunchKernelGGL(sf_special_sc(h->dev, sc), dim3((unsigned)grid_sc), dim3(pthreads), lds_sc, st, a); } }
+            if (grid_sc > L.ptiles) grid_sc = L.ptiles;
+            hipLaunchKernelGGL(sf_special_sc(h, sc), dim3((unsigned)grid_sc), dim3(pthreads), lds_sc, st, sa); } }
       else {
-         const sf_kernel_t sfk = sf_kernel(sf_wmax(h->dev), pthreads, sf_nv(h->dev));
-         hipLaunchKernelGGL(sfk, dim3((unsigned)pgrid), dim3(pthreads), h->dev.pk_lds, st, (const DevCfg *)h->d_dev, d_rows, (long long)nrows, ptiles,
-                            qtile, dirm, pkpool, hardp, hard_cap, &scratch->hard_count, scratch->scr); }
-      t1(kTSift);
+         const sf_kernel_t sfk = sf_kernel(sf_wmax(d), pthreads, sf_nv(d));
+         hipLaunchKernelGGL(sfk, dim3((unsigned)pgrid), dim3(pthreads), d.pk_lds, st, (const DevCfg *)h->d_dev, a.d_rows, nrows, L.ptiles,
+                            w.qtile, w.dir, w.pool, w.hard, L.hard_cap, &w.scratch->hard_count, w.scratch->scr); }
+      t1(kTSift); }
+   // the lists -> one stream of 16-byte records per (screen, head): the deferred candidates resolved (k_sift_hard), the streams' tile
+   // offsets (k_pscan), the records copied over with their absolute rows, volts and entry references (k_prep)
+   void launch_streams() {
+      t0(kTPrep);
+      const int nlists = d.nscreens * d.ntrks;
+      const int nsc = (int)((L.ptiles + 1023) / 1024);                    // chunks of 1024 tiles (k_pscan)
+      hipLaunchKernelGGL(k_sift_hard, dim3(h->num_cus * 16), dim3(256), 0, st, (const DevCfg *)h->d_dev, a.d_rows, nrows, (const SfHard *)w.hard, L.hard_cap,
+                         (const int *)&w.scratch->hard_count, w.ovf, w.extra, w.scratch->dbg2);
+      hipLaunchKernelGGL(k_pscan1, dim3(nsc), dim3(1024), 0, st, (const PeakDir *)w.dir, (const int *)w.extra, (int)L.ptiles, nlists, w.tstart, w.ctotc);
+      hipLaunchKernelGGL(k_pscan2, dim3(1), dim3(1024), 0, st, nsc, nlists, (const uint32_t *)w.ctotc, w.coff, w.ctot);
+      PrepArgs ppa; ppa.nlists = nlists; ppa.ntrks = d.ntrks; ppa.hcap = d.pk_slot; ppa.run = h->prep_run; ppa.mv = d.maxvolts;
+      // (workgroups per CU: 4 / 8 / 16 measured 0.51 / 0.47 / 0.42 ms for the span on C2 when half a wave took a list - the more lists in flight the better; a wave takes a
+      //  run of prep_run tiles of one stream now, RTFE_PREP_RUN, and 32 has not been tuned again for that shape)
+      hipLaunchKernelGGL(k_prep, dim3(h->num_cus * (h->prep_wgs >= 1 && h->prep_wgs <= 4096 ? h->prep_wgs : 32)), dim3(256), 0, st, ppa, (const PeakDir *)w.dir, (const unsigned char *)w.pool, (const unsigned char *)w.ovf,
+                         (const uint32_t *)w.tstart, (const uint32_t *)w.coff, (const uint32_t *)w.ctot, L.ptiles, L.ccap, w.crec, w.eref, w.work, L.work_cap, &w.scratch->prep_work);
+      hipLaunchKernelGGL(k_clear, dim3(h->num_cus * 4), dim3(256), 0, st, (const unsigned long long *)w.work, L.work_cap, (const int *)&w.scratch->prep_work, (const uint32_t *)w.ctot, L.ccap, w.crec);
+#ifdef RTFE_CPU_EMUL
+      if (getenv("RTFE_PREP_CHECK")) hipLaunchKernelGGL(k_prep_check, dim3(1), dim3(64), 0, st, (const DevCfg *)h->d_dev, (const uint32_t *)w.ctot, L.ccap, (const CRec *)w.crec);
+      if (getenv("RTFE_PREP_CHECK") && atoi(getenv("RTFE_PREP_CHECK")) > 1)
+         hipLaunchKernelGGL(k_prep_shapes, dim3(1), dim3(64), 0, st, nlists, (int)d.pk_slot, h->prep_run, L.ptiles, L.ccap, (const PeakDir *)w.dir, (const unsigned char *)w.pool, (const uint32_t *)w.ctot);
+#endif
+      t1(kTPrep); }
+   // the chains: from the restart row until the baseline is fixed (k_gain, mode 0), the steady stretch (k_gain_s), whatever that stopped at (k_gain, mode 1)
+   void launch_chains() {
+      t0(kTGain);
+      for (int mode = 0; mode < 2; ++mode) {
+         if (mode == 1) t0(kTGainTail);
+         hipLaunchKernelGGL(k_gain, dim3(h->num_cus * 4), dim3(64), 0, st, (const DevCfg *)h->d_dev, mode, w.cst, nrows, row_base, (const rtfe_burst *)a.d_bursts,
+                            w.scratch, w.ctl, a.d_counts, a.d_events, w.chain, (const CRec *)w.crec, (const uint2 *)w.eref, (const uint32_t *)w.tstart, (const uint32_t *)w.coff, (const uint32_t *)w.ctot, L.ccap,
+                            (const unsigned char *)w.pool, L.ptiles, w.segs, L.seg_cap, a.d_rows);
+         if (mode == 0) {
+            t1(kTGain); t0(kTGainS);
+            // the steady stretches: in segments, every one on its own, joined where the states agree bit for bit (rtfe_gain.hip)
+            hipLaunchKernelGGL(k_gain_seg, dim3(h->num_cus * 16), dim3(64), 0, st, (const DevCfg *)h->d_dev, (const ChainSt *)w.cst, w.scratch, (const CRec *)w.crec, L.ccap, w.segs, (const int *)&w.scratch->nsegs, L.seg_cap, w.gfire);
+            hipLaunchKernelGGL(k_gain_join, dim3(h->num_cus * 2), dim3(64), 0, st, (const DevCfg *)h->d_dev, w.cst, (const rtfe_burst *)a.d_bursts, w.scratch, (const BurstCtl *)w.ctl, a.d_counts, w.chain, w.segs);
+            t1(kTGainS); } }
+#ifdef RTFE_CPU_EMUL
+      if (getenv("RTFE_PREP_CHECK") && atoi(getenv("RTFE_PREP_CHECK")) > 1 && d.pk_seg_recs > 0)
+         hipLaunchKernelGGL(k_seg_shapes, dim3(1), dim3(64), 0, st, (const DevCfg *)h->d_dev, (const ChainSt *)w.cst, (const BurstScratch *)w.scratch, (const CRec *)w.crec, L.ccap,
+                            (const GsSeg *)w.segs, L.seg_cap, (const float *)w.gfire);
+#endif
+      t1(kTGainTail); }
+   // the heads' and tails' noted events (k_emit: a wave per chain at a time - a chain's head and tail hold a few dozen) are finished on the side stream
+   // beside the segments' events (k_emit_seg): disjoint parts of the event lists, both only need the chains
+   void launch_emit(hipStream_t side) {
+      t0(kTEmit);
+      hipStream_t se = st;
+      if (side != st) { se = side; (void)hipEventRecord(h->ev_fork2, st); (void)hipStreamWaitEvent(se, h->ev_fork2, 0); }
+      hipLaunchKernelGGL(k_emit, dim3(h->num_cus * 32), dim3(64), 0, se, h->d_dev, (const rtfe_burst *)a.d_bursts, (const BurstScratch *)w.scratch, (const BurstCtl *)w.ctl, (const uint32_t *)a.d_counts, a.d_events,
+                         (const float *)w.chain, (const CRec *)w.crec, (const uint2 *)w.eref, L.ccap, (const unsigned char *)w.pool, (const ChainSt *)w.cst, a.d_rows, nrows, (const GsSeg *)w.segs);
+      if (se != st) (void)hipEventRecord(h->ev_join2, se);
+      hipLaunchKernelGGL(k_emit_seg, dim3(h->num_cus * 16), dim3(256), 0, st, (const DevCfg *)h->d_dev, (const ChainSt *)w.cst, (const BurstCtl *)w.ctl, a.d_events, (const CRec *)w.crec, (const uint2 *)w.eref, L.ccap,
+                         (const unsigned char *)w.pool, (const GsSeg *)w.segs, (const int *)&w.scratch->nsegs, L.seg_cap, (const float *)w.gfire, (int)(L.max_bursts * d.nparm * d.ntrks), a.d_rows, nrows);
+      if (se != st) (void)hipStreamWaitEvent(st, h->ev_join2, 0);
+      hipLaunchKernelGGL(k_publish, dim3(h->num_cus < 64 ? h->num_cus : 64), dim3(256), 0, st, h->d_dev, nrows, a.d_bursts, w.scratch, w.ctl);
+      if (d.nuset < d.nparm)      // parameter sets the front end cannot tell apart were ONE chain: its events into the other sets' regions
+         hipLaunchKernelGGL(k_dup_sets, dim3(h->num_cus * 8), dim3(256), 0, st, (const DevCfg *)h->d_dev, (const rtfe_burst *)a.d_bursts, (const BurstScratch *)w.scratch, (const BurstCtl *)w.ctl, a.d_counts, a.d_events);
+      t1(kTEmit); }
+   // ---- the peak path: k_sift (quiet map + records) -> k_bursts -> k_zones -> k_gain -> k_emit -> k_publish -> whatever the chains gave up ----
+   void launch_peak_path() {
+      const int stop_after = h->peak_stop;
+      // the scratch block and the deferred candidates' counts cleared, and - a handle's first scan - the screen's floor estimated from the samples (k_scan_begin)
+      uint4 *const extra16 = ws_at<uint4>(a.d_workspace, L.extra);      // (the whole region, in 16-byte units)
+      hipLaunchKernelGGL(k_scan_begin, dim3(h->num_cus * 4), dim3(256), 0, st, h->d_dev, w.scratch, extra16, (long long)((L.cst - L.extra) / 16), a.d_rows, nrows);
+      launch_sift();
       // Two things only need k_sift's output and not each other: (a) quiet map -> burst table -> restart rows (k_qpack, k_bursts, k_zones:
       // latency-bound, a workgroup or a wave per burst) and (b) the lists -> the streams (k_sift_hard, k_pscan, k_prep).  (a) runs on a
       // stream of the handle's own beside (b) and joins in front of the chains (RTFE_OVERLAP=0: in line; its span then is work, else the
@@ -744,171 +816,97 @@ static int scan_launch(rtfe_handle *h, const int16_t *d_rows, int64_t nrows, int
          ensure_side(h);
          if (h->side) { sa = h->side; (void)hipEventRecord(h->ev_fork, st); (void)hipStreamWaitEvent(sa, h->ev_fork, 0); } }
       t0s(kTBursts, sa);
-      hipLaunchKernelGGL(k_qpack, dim3(h->num_cus < 64 ? h->num_cus : 64), dim3(256), 0, sa, (const uint16_t *)qtile, ptiles, qwords, nwords);
-      launch_bursts(h, sa, qwords, nwords, nchunks, nrows, own_rows, first_is_tape_start, event_capacity, d_bursts,
-                    (long long)(max_bursts < rtfe_max_bursts(h, nrows) ? max_bursts : rtfe_max_bursts(h, nrows)), scratch, d_nbursts, reinterpret_cast<uint32_t *>(wsb + ws_rtot_off(h, nrows)));
-      if (stop_after >= 3) {
-         hipLaunchKernelGGL(k_zones, dim3(h->num_cus * 8), dim3(64), 0, sa, h->d_dev, d_rows, (long long)nrows, (const rtfe_burst *)d_bursts,
-                            (const BurstScratch *)scratch, ctlp);
-         if (h->dev.invert)      // (an inverted -32768 is +32768, wider than a record: bursts that hold one go to the sample path's literal walk)
-            hipLaunchKernelGGL(k_rails, dim3(h->num_cus * 8), dim3(64), 0, sa, h->d_dev, d_rows, (long long)nrows, (const rtfe_burst *)d_bursts,
-                               (const BurstScratch *)scratch, ctlp); }
+      hipLaunchKernelGGL(k_qpack, dim3(h->num_cus < 64 ? h->num_cus : 64), dim3(256), 0, sa, (const uint16_t *)w.qtile, L.ptiles, w.qwords, L.nwords);
+      launch_bursts(sa);
+      if (stop_after >= 3) launch_zones(sa);
       t1s(kTBursts, sa);
       if (sa != st) (void)hipEventRecord(h->ev_join, sa);
-      // the lists -> one stream of 16-byte records per (screen, head): the deferred candidates resolved (k_sift_hard), the streams' tile
-      // offsets (k_pscan), the records copied over with their absolute rows, volts and entry references (k_prep)
-      t0(kTPrep);
-      const int nlists = h->dev.nscreens * h->dev.ntrks;
-      uint32_t *tstartp = reinterpret_cast<uint32_t *>(wsb + ws_pktstart_off(h, nrows));
-      const int nsc = (int)((ptiles + 1023) / 1024);                    // chunks of 1024 tiles (k_pscan)
-      uint32_t *ctotcp = tstartp + (size_t)ptiles * nlists, *coffp = ctotcp + (size_t)nsc * nlists, *ctotp = coffp + (size_t)nsc * nlists;
-      CRec *crecp = reinterpret_cast<CRec *>(wsb + ws_pkcrec_off(h, nrows));
-      uint2 *erefp = reinterpret_cast<uint2 *>(wsb + ws_pkeref_off(h, nrows));
-      int *extrap = reinterpret_cast<int *>(wsb + ws_pkextra_off(h, nrows));
-      const long long ccap = pk_ccap(h, nrows);
-      hipLaunchKernelGGL(k_sift_hard, dim3(h->num_cus * 16), dim3(256), 0, st, (const DevCfg *)h->d_dev, d_rows, (long long)nrows, (const SfHard *)hardp, hard_cap,
-                         (const int *)&scratch->hard_count, ovfp, extrap, scratch->dbg2);
-      hipLaunchKernelGGL(k_pscan1, dim3(nsc), dim3(1024), 0, st, (const PeakDir *)dirm, (const int *)extrap, (int)ptiles, nlists, tstartp, ctotcp);
-      hipLaunchKernelGGL(k_pscan2, dim3(1), dim3(1024), 0, st, nsc, nlists, (const uint32_t *)ctotcp, coffp, ctotp);
-      PrepArgs ppa; ppa.nlists = nlists; ppa.ntrks = h->dev.ntrks; ppa.hcap = h->dev.pk_slot; ppa.run = h->prep_run; ppa.mv = h->dev.maxvolts;
-      // (workgroups per CU: 4 / 8 / 16 measured 0.51 / 0.47 / 0.42 ms for the span on C2 when half a wave took a list - the more lists in flight the better; a wave takes a
-      //  run of prep_run tiles of one stream now, RTFE_PREP_RUN, and 32 has not been tuned again for that shape)
-      hipLaunchKernelGGL(k_prep, dim3(h->num_cus * (h->prep_wgs >= 1 && h->prep_wgs <= 4096 ? h->prep_wgs : 32)), dim3(256), 0, st, ppa, (const PeakDir *)dirm, (const unsigned char *)pkpool, (const unsigned char *)ovfp,
-                         (const uint32_t *)tstartp, (const uint32_t *)coffp, (const uint32_t *)ctotp, ptiles, ccap, crecp, erefp,
-                         reinterpret_cast<unsigned long long *>(wsb + ws_pkgfire_off(h, nrows)), pk_work_cap(h, nrows), &scratch->prep_work);
-      // (the work list lives where k_gain_seg's gains will: nothing reads it behind k_clear)
-      hipLaunchKernelGGL(k_clear, dim3(h->num_cus * 4), dim3(256), 0, st, (const unsigned long long *)(wsb + ws_pkgfire_off(h, nrows)), pk_work_cap(h, nrows), (const int *)&scratch->prep_work,
-                         (const uint32_t *)ctotp, ccap, crecp);
-#ifdef RTFE_CPU_EMUL
-      if (getenv("RTFE_PREP_CHECK")) hipLaunchKernelGGL(k_prep_check, dim3(1), dim3(64), 0, st, (const DevCfg *)h->d_dev, (const uint32_t *)ctotp, ccap, (const CRec *)crecp);
-      if (getenv("RTFE_PREP_CHECK") && atoi(getenv("RTFE_PREP_CHECK")) > 1)
-         hipLaunchKernelGGL(k_prep_shapes, dim3(1), dim3(64), 0, st, nlists, (int)h->dev.pk_slot, h->prep_run, ptiles, ccap, (const PeakDir *)dirm, (const unsigned char *)pkpool, (const uint32_t *)ctotp);
-#endif
-      t1(kTPrep);
+      launch_streams();
       if (sa != st) (void)hipStreamWaitEvent(st, h->ev_join, 0);        // join: the chains need both
-      if (stop_after < 3) { skip_rest(); return launch_check("rtfe_scan"); }
-      t0(kTGain);
-      ChainSt *cstp = reinterpret_cast<ChainSt *>(wsb + ws_pkcst_off(h, nrows));
-      // the chains: from the restart row until the baseline is fixed (k_gain, mode 0), the steady stretch (k_gain_s), whatever that stopped at (k_gain, mode 1)
-      for (int mode = 0; mode < 2; ++mode) {
-         if (mode == 1) t0(kTGainTail);
-         hipLaunchKernelGGL(k_gain, dim3(h->num_cus * 4), dim3(64), 0, st, (const DevCfg *)h->d_dev, mode, cstp, (long long)nrows, (long long)row_base, (const rtfe_burst *)d_bursts,
-                            scratch, ctlp, d_counts, d_events, chainh, (const CRec *)crecp, (const uint2 *)erefp, (const uint32_t *)tstartp, (const uint32_t *)coffp, (const uint32_t *)ctotp, ccap,
-                            (const unsigned char *)pkpool, ptiles, reinterpret_cast<GsSeg *>(wsb + ws_pksegs_off(h, nrows)), pk_seg_cap(h, nrows), (const int16_t *)d_rows);
-         if (mode == 0) {
-            t1(kTGain); t0(kTGainS);
-            // the steady stretches: in segments, every one on its own, joined where the states agree bit for bit (rtfe_gain.hip)
-            GsSeg *segp = reinterpret_cast<GsSeg *>(wsb + ws_pksegs_off(h, nrows));
-            float *gfirep = reinterpret_cast<float *>(wsb + ws_pkgfire_off(h, nrows));
-            hipLaunchKernelGGL(k_gain_seg, dim3(h->num_cus * 16), dim3(64), 0, st, (const DevCfg *)h->d_dev, (const ChainSt *)cstp, scratch, (const CRec *)crecp, ccap, segp, (const int *)&scratch->nsegs, pk_seg_cap(h, nrows), gfirep);
-            hipLaunchKernelGGL(k_gain_join, dim3(h->num_cus * 2), dim3(64), 0, st, (const DevCfg *)h->d_dev, cstp, (const rtfe_burst *)d_bursts, scratch, (const BurstCtl *)ctlp, d_counts, chainh, segp);
-            t1(kTGainS); } }
-#ifdef RTFE_CPU_EMUL
-      if (getenv("RTFE_PREP_CHECK") && atoi(getenv("RTFE_PREP_CHECK")) > 1 && h->dev.pk_seg_recs > 0)
-         hipLaunchKernelGGL(k_seg_shapes, dim3(1), dim3(64), 0, st, (const DevCfg *)h->d_dev, (const ChainSt *)cstp, (const BurstScratch *)scratch, (const CRec *)crecp, ccap,
-                            (const GsSeg *)(wsb + ws_pksegs_off(h, nrows)), pk_seg_cap(h, nrows), (const float *)(wsb + ws_pkgfire_off(h, nrows)));
-#endif
-      t1(kTGainTail);
-      if (stop_after < 4) { skip_rest(); return launch_check("rtfe_scan"); }
-      t0(kTEmit);
-      // the heads' and tails' noted events (k_emit: a wave per chain at a time - a chain's head and tail hold a few dozen) are finished on the side stream
-      // beside the segments' events (k_emit_seg): disjoint parts of the event lists, both only need the chains
-      hipStream_t se = st;
-      if (sa != st) { se = sa; (void)hipEventRecord(h->ev_fork2, st); (void)hipStreamWaitEvent(se, h->ev_fork2, 0); }
-      hipLaunchKernelGGL(k_emit, dim3(h->num_cus * 32), dim3(64), 0, se,
-                         h->d_dev, (const rtfe_burst *)d_bursts, (const BurstScratch *)scratch,
-                         (const BurstCtl *)ctlp, (const uint32_t *)d_counts, d_events, (const float *)chainh, (const CRec *)crecp, (const uint2 *)erefp, ccap, (const unsigned char *)pkpool, (const ChainSt *)cstp, d_rows, (long long)nrows, (const GsSeg *)(wsb + ws_pksegs_off(h, nrows)));
-      if (se != st) (void)hipEventRecord(h->ev_join2, se);
-      hipLaunchKernelGGL(k_emit_seg, dim3(h->num_cus * 16), dim3(256), 0, st, (const DevCfg *)h->d_dev, (const ChainSt *)cstp, (const BurstCtl *)ctlp, d_events, (const CRec *)crecp, (const uint2 *)erefp, ccap,
-                         (const unsigned char *)pkpool, (const GsSeg *)(wsb + ws_pksegs_off(h, nrows)), (const int *)&scratch->nsegs, pk_seg_cap(h, nrows), (const float *)(wsb + ws_pkgfire_off(h, nrows)), (int)(rtfe_max_bursts(h, nrows) * h->dev.nparm * h->dev.ntrks), d_rows, (long long)nrows);
-      if (se != st) (void)hipStreamWaitEvent(st, h->ev_join2, 0);
-      hipLaunchKernelGGL(k_publish, dim3(h->num_cus < 64 ? h->num_cus : 64), dim3(256), 0, st, h->d_dev, (long long)nrows, d_bursts, scratch, ctlp);
-      if (h->dev.nuset < h->dev.nparm)      // parameter sets the front end cannot tell apart were ONE chain: its events into the other sets' regions
-         hipLaunchKernelGGL(k_dup_sets, dim3(h->num_cus * 8), dim3(256), 0, st, (const DevCfg *)h->d_dev, (const rtfe_burst *)d_bursts, (const BurstScratch *)scratch, (const BurstCtl *)ctlp, d_counts, d_events);
-      t1(kTEmit);
-      if (stop_after < 5) { skip_rest(); return launch_check("rtfe_scan"); }
-      t0(kTDecode);
-      hipLaunchKernelGGL(k_decode, dim3(dgrid), dim3(threads), h->lds_bytes, st, h->d_dev, d_rows, (long long)nrows,
-                         (long long)row_base, d_bursts, scratch, d_counts, d_events, 0xffffffffu, 0, 0, (int)kDecodeRedo, ctlp);
-      t1(kTDecode);
-      if (h->dev.adapt_floor) hipLaunchKernelGGL(k_adapt_floor, dim3(1), dim3(1), 0, st, h->d_dev, (const BurstScratch *)scratch);      // (the NEXT scan's screen)
-      skip_rest();
-      return launch_check("rtfe_scan"); }
-   // ---- the sample path: quiet map -> bursts -> every burst in one pass over its samples ----
-   (void)hipMemsetAsync(scratch, 0, kScratchBytes, st);
-   const long long dtiles = ds_tiles_for(nrows);
-   unsigned char *deadp = reinterpret_cast<unsigned char *>(wsb + ws_dsdead_off(h, nrows));
-   unsigned char *slotp = reinterpret_cast<unsigned char *>(wsb + ws_dsslot_off(h, nrows));
-   if (h->dev.dense_path) {
-      // PE, GCR peak detection (rtfe_dense.hip): the dense pass first - it reads every row anyway, and leaves the quiet map's bits as well
-      // (k_quiet folded in: one pass over the tape less); bursts and restart rows behind it, then a lane per chain
-      (void)hipMemsetAsync(qwords, 0, (size_t)nwords * 8, st);         // (a tile writes its own byte: the map's tail stays "not quiet")
-      const int dlds = (int)ds_lds_layout(h->dev.ntrks, h->dev.halo_rows, h->dev.ds_pad + kDsTile + kDsRight, h->dev.ds_up).total + 64;
-      int dpc = (160 * 1024) / (dlds + 1024);
-      if (dpc > 8) dpc = 8;
+      if (stop_after < 3) return;
+      launch_chains();
+      if (stop_after < 4) return;
+      launch_emit(sa);
+      if (stop_after < 5) return;
+      launch_decode(kDecodeRedo);
+      if (d.adapt_floor) hipLaunchKernelGGL(k_adapt_floor, dim3(1), dim3(1), 0, st, h->d_dev, (const BurstScratch *)w.scratch); }      // (the NEXT scan's screen)
+   // ---- the dense sample path, PE and GCR peak detection (rtfe_dense.hip): the dense pass first - it reads every row anyway, and leaves the quiet map's bits
+   // as well (k_quiet folded in: one pass over the tape less); bursts and restart rows behind it, then a lane per chain, then whatever the chains gave up ----
+   void launch_dense_path() {
+      (void)hipMemsetAsync(w.scratch, 0, kScratchBytes, st);
+      (void)hipMemsetAsync(w.qwords, 0, (size_t)L.nwords * 8, st);         // (a tile writes its own byte: the map's tail stays "not quiet")
+      const int dlds = (int)ds_lds_layout(d.ntrks, d.halo_rows, d.ds_pad + kDsTile + kDsRight, d.ds_up).total + 64;
+      int dpc = lds_wgs_per_cu(dlds, 1024, 8);
       if (h->dseg_wgs >= 1 && h->dseg_wgs < dpc) dpc = h->dseg_wgs;
       if (dpc < 1) dpc = 1;
       long long dg = (long long)h->num_cus * dpc;
-      if (dg > dtiles) dg = dtiles;
+      if (dg > L.dtiles) dg = L.dtiles;
       t0(kTDseg);
       // (threads: fewer waves that fill the rounds of the all-lane phases better - 448 / 384 / 320 threads for 9 tracks - are SLOWER: G1's k_dseg 84.8 / 92.1 / 93.8 ms
       //  against 78.3 with 512: the kernel lives on its resident waves, not on its lane-task count; RTFE_DSEG_THREADS for experiments)
       int dthreads = kDsThreads;
       if (h->dseg_threads >= 64 && h->dseg_threads <= kDsThreads) dthreads = h->dseg_threads / 64 * 64;
-      hipLaunchKernelGGL(ds_kernel(h->dev.ntrks), dim3((unsigned)dg), dim3(dthreads), dlds, st, (const DevCfg *)h->d_dev, d_rows, (long long)nrows, dtiles, deadp, reinterpret_cast<unsigned char *>(qwords), slotp, scratch->scr);
-      t1(kTDseg); }
-   else {
-      t0(kTQuiet);
-      hipLaunchKernelGGL(k_quiet, dim3(grid), dim3(256), 0, st, d_rows, (long long)nrows, h->dev.ntrks, h->dev.quiet_i, qwords, nwords);
-      t1(kTQuiet); }
-   t0(kTBursts);
-   launch_bursts(h, st, qwords, nwords, nchunks, nrows, own_rows, first_is_tape_start, event_capacity, d_bursts,
-                 (long long)(max_bursts < rtfe_max_bursts(h, nrows) ? max_bursts : rtfe_max_bursts(h, nrows)), scratch, d_nbursts, reinterpret_cast<uint32_t *>(wsb + ws_rtot_off(h, nrows)));
-   if (h->dev.dense_path) {                                            // the restart rows of all bursts (rtfe_gain.hip)
-      hipLaunchKernelGGL(k_zones, dim3(h->num_cus * 8), dim3(64), 0, st, h->d_dev, d_rows, (long long)nrows, (const rtfe_burst *)d_bursts,
-                         (const BurstScratch *)scratch, ctlp);
-      if (h->dev.invert)
-         hipLaunchKernelGGL(k_rails, dim3(h->num_cus * 8), dim3(64), 0, st, h->d_dev, d_rows, (long long)nrows, (const rtfe_burst *)d_bursts,
-                            (const BurstScratch *)scratch, ctlp); }
-   t1(kTBursts);
-   if (h->dev.find_zeros && !h->dev.differentiate && h->zeros_kernel) {          // -zeros: the lean kernel of its own (rtfe_zeros.hip)
-      t0(kTZeros);
-      const dim3 zg(h->num_cus * (RTFE_ZP_WPS * 256 / kZpThreads)), zb(kZpThreads);                     // persistent workgroups, a burst at a time
-      if (h->dev.ntrks == 9) hipLaunchKernelGGL(k_zeros<9>, zg, zb, 0, st, (const DevCfg *)h->d_dev, d_rows, (long long)nrows, (long long)row_base, d_bursts, scratch, d_counts, d_events);
-      else if (h->dev.ntrks == 7) hipLaunchKernelGGL(k_zeros<7>, zg, zb, 0, st, (const DevCfg *)h->d_dev, d_rows, (long long)nrows, (long long)row_base, d_bursts, scratch, d_counts, d_events);
-      else hipLaunchKernelGGL(k_zeros<0>, zg, zb, 0, st, (const DevCfg *)h->d_dev, d_rows, (long long)nrows, (long long)row_base, d_bursts, scratch, d_counts, d_events);
-      t1(kTZeros); }
-   else if (h->diffz_kernel) {                                        // -zeros -differentiate: the transducer kernel (rtfe_diffz.hip), in the k_zeros span
-      t0(kTZeros);
-      hipLaunchKernelGGL(k_diffz, dim3(h->num_cus * 6), dim3(kDzThreads), 0, st, (const DevCfg *)h->d_dev, d_rows, (long long)nrows, (long long)row_base, d_bursts, scratch, d_counts, d_events);
-      t1(kTZeros); }
-   else if (h->dev.dense_path) {                                      // PE, GCR peak detection: sub-segment lists, then a lane per chain (rtfe_dense.hip)
-      const int dstop = h->dense_stop;      // (debugging: 1 = stop behind k_dseg, 2 = behind k_dchain)
-      if (dstop < 2) { skip_rest(); return launch_check("rtfe_scan"); }
+      unsigned char *const qbytes = ws_at<unsigned char>(a.d_workspace, L.qwords);      // (the quiet map as k_dseg writes it: a byte a tile)
+      hipLaunchKernelGGL(ds_kernel(h), dim3((unsigned)dg), dim3(dthreads), dlds, st, (const DevCfg *)h->d_dev, a.d_rows, nrows, L.dtiles, w.dead, qbytes, w.slot, w.scratch->scr);
+      t1(kTDseg);
+      t0(kTBursts);
+      launch_bursts(st);
+      launch_zones(st);
+      t1(kTBursts);
+      if (h->dense_stop < 2) return;      // (debugging: 1 = stop behind k_dseg, 2 = behind k_dchain)
       t0(kTDchain);
-      const int ds_order = h->ds_order;      // (0: the chains in burst order)
-      if (ds_order) hipLaunchKernelGGL(k_dorder, dim3(1), dim3(1024), 0, st, (const rtfe_burst *)d_bursts, (const BurstScratch *)scratch, ctlp, (long long)nrows);
+      if (h->ds_order) hipLaunchKernelGGL(k_dorder, dim3(1), dim3(1024), 0, st, (const rtfe_burst *)a.d_bursts, (const BurstScratch *)w.scratch, w.ctl, nrows);
       // (LDS per wave decides how many chains run side by side - the kernel holds ~240 VGPRs, eight waves per CU: the literal rows' cache is a chunk and the
       //  widest window + 2, not the 88 rows the widest window the library accepts would need)
       int wmax = 1;
-      for (int i = 0; i < h->dev.nparm; ++i) if (h->dev.parm[i].W > wmax) wmax = h->dev.parm[i].W;
+      for (int i = 0; i < d.nparm; ++i) if (d.parm[i].W > wmax) wmax = d.parm[i].W;
       const int dcache = wmax + 2 + kDcChunk < kDcCache ? ((wmax + 2 + kDcChunk + 7) & ~7) : kDcCache;
-      const int dc_wgs = h->dchain_wgs;      // (waves per CU that take chains from the queue)
-      hipLaunchKernelGGL(k_dchain, dim3(h->num_cus * (dc_wgs >= 1 && dc_wgs <= 64 ? dc_wgs : 16)), dim3(64), (size_t)(h->dev.ds_slot < 144 ? 144 : h->dev.ds_slot) * 64 + (size_t)dcache * 64 * 2, st, (const DevCfg *)h->d_dev, d_rows, (long long)nrows, (long long)row_base, (const rtfe_burst *)d_bursts,
-                         scratch, ctlp, d_counts, d_events, (const unsigned char *)deadp, (const unsigned char *)slotp, dtiles, ds_order);
-      hipLaunchKernelGGL(k_publish, dim3(h->num_cus < 64 ? h->num_cus : 64), dim3(256), 0, st, h->d_dev, (long long)nrows, d_bursts, scratch, ctlp);
+      hipLaunchKernelGGL(k_dchain, dim3(h->num_cus * (h->dchain_wgs >= 1 && h->dchain_wgs <= 64 ? h->dchain_wgs : 16)), dim3(64), (size_t)(d.ds_slot < 144 ? 144 : d.ds_slot) * 64 + (size_t)dcache * 64 * 2, st, (const DevCfg *)h->d_dev, a.d_rows, nrows, row_base, (const rtfe_burst *)a.d_bursts,
+                         w.scratch, w.ctl, a.d_counts, a.d_events, (const unsigned char *)w.dead, (const unsigned char *)w.slot, L.dtiles, h->ds_order);
+      hipLaunchKernelGGL(k_publish, dim3(h->num_cus < 64 ? h->num_cus : 64), dim3(256), 0, st, h->d_dev, nrows, a.d_bursts, w.scratch, w.ctl);
       t1(kTDchain);
-      if (dstop < 3) { skip_rest(); return launch_check("rtfe_scan"); }
-      t0(kTDecode);
-      hipLaunchKernelGGL(k_decode, dim3(dgrid), dim3(threads), h->lds_bytes, st, h->d_dev, d_rows, (long long)nrows,
-                         (long long)row_base, d_bursts, scratch, d_counts, d_events, 0xffffffffu, 0, 0, (int)kDecodeRedo, ctlp);
-      t1(kTDecode); }
-   else {                                                             // differentiated peaks, density detection (and PE / GCR with RTFE_DENSE_PATH=0)
-      t0(kTDecode);
-      hipLaunchKernelGGL(k_decode, dim3(dgrid), dim3(threads), h->lds_bytes, st, h->d_dev, d_rows, (long long)nrows,
-                         (long long)row_base, d_bursts, scratch, d_counts, d_events, 0xffffffffu, 0, 0, (int)kDecodeAll, ctlp);
-      t1(kTDecode); }
-   skip_rest();
+      if (h->dense_stop < 3) return;
+      launch_decode(kDecodeRedo); }
+   // ---- the sample path: quiet map -> bursts -> every burst in one pass over its samples (-zeros: k_zeros; -zeros -differentiate: k_diffz; differentiated peaks,
+   // density detection, PE / GCR with RTFE_DENSE_PATH=0: k_decode) ----
+   void launch_sample_path() {
+      (void)hipMemsetAsync(w.scratch, 0, kScratchBytes, st);
+      const int grid = (int)(L.nwords < (long long)h->num_cus * 8 ? L.nwords : (long long)h->num_cus * 8);
+      t0(kTQuiet);
+      hipLaunchKernelGGL(k_quiet, dim3(grid), dim3(256), 0, st, a.d_rows, nrows, d.ntrks, d.quiet_i, w.qwords, L.nwords);
+      t1(kTQuiet);
+      t0(kTBursts);
+      launch_bursts(st);
+      t1(kTBursts);
+      if (d.find_zeros && !d.differentiate && h->zeros_kernel) {          // -zeros: the lean kernel of its own (rtfe_zeros.hip)
+         t0(kTZeros);
+         hipLaunchKernelGGL(zeros_kernel(d.ntrks), dim3(h->num_cus * (RTFE_ZP_WPS * 256 / kZpThreads)), dim3(kZpThreads), 0, st,      // persistent workgroups, a burst at a time
+                            (const DevCfg *)h->d_dev, a.d_rows, nrows, row_base, a.d_bursts, w.scratch, a.d_counts, a.d_events);
+         t1(kTZeros); }
+      else if (h->diffz_kernel) {                                        // -zeros -differentiate: the transducer kernel (rtfe_diffz.hip), in the k_zeros span
+         t0(kTZeros);
+         hipLaunchKernelGGL(k_diffz, dim3(h->num_cus * 6), dim3(kDzThreads), 0, st, (const DevCfg *)h->d_dev, a.d_rows, nrows, row_base, a.d_bursts, w.scratch, a.d_counts, a.d_events);
+         t1(kTZeros); }
+      else launch_decode(kDecodeAll); } };
+
+static int scan_launch(rtfe_handle *h, const ScanArgs &a) {
+   if (!h || !a.d_rows || !a.d_workspace || !a.d_bursts || !a.d_nbursts || !a.d_counts || !a.d_events) return fail(-1, "null argument");
+   if (h->dev.mode == RTFE_WW) return fail(-44, "Whirlwind tapes have no independent bursts: use rtfe_ww_scan");
+   if (((uintptr_t)a.d_rows & 15) != 0) return fail(-31, "d_rows must be 16-byte aligned");
+   const WsLayout L = ws_layout(h, a.nrows);
+   if (a.workspace_bytes < L.total) return fail(-32, "workspace too small");
+   // the peak path addresses rows with 32 bits and a record's margin entries by a 32-bit index (2-byte units) into pool + overflow slots
+   if (h->dev.peak_path && (a.nrows >= 0x7ff00000ll || (L.qtile - L.pool) / 2 >= 0xffffffffull))
+      return fail(-36, "%lld rows are too many for one rtfe_scan on the peak path: scan the tape in fragments (own_rows)", (long long)a.nrows);
+   if (a.nrows <= 0 || a.max_bursts < 1) return fail(-33, "nothing to scan");
+   if (a.own_rows <= 0 || a.own_rows > a.nrows) return fail(-35, "own_rows must be in (0, nrows]");
+   Scan s = {h, h->dev, a, (hipStream_t)a.stream, L, ws_view(h, L, a.d_workspace), a.nrows, a.row_base, a.nrows / kChunkRows,
+             a.max_bursts < L.max_bursts ? a.max_bursts : L.max_bursts, h->timing ? h->ev_next : 0, {false}};
+   if (h->timing) { h->ev_next = (h->ev_next + 1) % kTimingRing; ++h->ev_pending; }
+   if (h->dev.peak_path) s.launch_peak_path();
+   else if (h->dev.dense_path) s.launch_dense_path();
+   else s.launch_sample_path();
+   s.skip_rest();      // (also behind RTFE_PEAK_STOP / RTFE_DENSE_STOP: the spans that did not run)
    return launch_check("rtfe_scan"); }
 
 extern "C" int rtfe_set_graphs(rtfe_handle *h, int enable) {
@@ -920,14 +918,13 @@ extern "C" int rtfe_scan(rtfe_handle *h, const int16_t *d_rows, int64_t nrows, i
                          void *d_workspace, size_t workspace_bytes,
                          rtfe_burst *d_bursts, int64_t max_bursts, int32_t *d_nbursts,
                          uint32_t *d_counts, rtfe_event *d_events, int64_t event_capacity, void *stream) {
+   const ScanArgs a = {d_rows, nrows, own_rows, row_base, first_is_tape_start, d_workspace, workspace_bytes, d_bursts, max_bursts, d_nbursts, d_counts, d_events, event_capacity, stream};
    // (per-kernel timing records events between the launches, the debug counters are read by tools between scans, the legacy default stream cannot be
    //  captured: those scans are launched directly)
-   if (!h || !h->graphs || h->timing || h->dev.debug || !stream)
-      return scan_launch(h, d_rows, nrows, own_rows, row_base, first_is_tape_start, d_workspace, workspace_bytes, d_bursts, max_bursts, d_nbursts, d_counts, d_events, event_capacity, stream);
+   if (!h || !h->graphs || h->timing || h->dev.debug || !stream) return scan_launch(h, a);
    hipStream_t st = (hipStream_t)stream;
-   const unsigned long long key[13] = {(unsigned long long)(uintptr_t)d_rows, (unsigned long long)nrows, (unsigned long long)own_rows, (unsigned long long)row_base, (unsigned long long)first_is_tape_start,
-                                       (unsigned long long)(uintptr_t)d_workspace, (unsigned long long)workspace_bytes, (unsigned long long)(uintptr_t)d_bursts, (unsigned long long)max_bursts,
-                                       (unsigned long long)(uintptr_t)d_nbursts, (unsigned long long)(uintptr_t)d_counts, (unsigned long long)(uintptr_t)d_events, (unsigned long long)event_capacity};
+   unsigned long long key[13];
+   graph_key(a, key);
    for (int i = 0; i < kGraphCache; ++i) {
       rtfe_handle::GraphEnt &e = h->gcache[i];
       if (e.exec && memcmp(e.key, key, sizeof key) == 0) {
@@ -942,8 +939,8 @@ extern "C" int rtfe_scan(rtfe_handle *h, const int16_t *d_rows, int64_t nrows, i
    ensure_side(h);
    if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) != hipSuccess) {
       (void)hipGetLastError(); h->graphs = 0;
-      return scan_launch(h, d_rows, nrows, own_rows, row_base, first_is_tape_start, d_workspace, workspace_bytes, d_bursts, max_bursts, d_nbursts, d_counts, d_events, event_capacity, stream); }
-   const int rc = scan_launch(h, d_rows, nrows, own_rows, row_base, first_is_tape_start, d_workspace, workspace_bytes, d_bursts, max_bursts, d_nbursts, d_counts, d_events, event_capacity, stream);
+      return scan_launch(h, a); }
+   const int rc = scan_launch(h, a);
    hipGraph_t g = nullptr;
    const hipError_t ec = hipStreamEndCapture(st, &g);
    if (rc != 0) { if (g) (void)hipGraphDestroy(g); (void)hipGetLastError(); return rc; }      // (an argument the scan refuses: nothing was enqueued, the message stands)
@@ -952,7 +949,7 @@ extern "C" int rtfe_scan(rtfe_handle *h, const int16_t *d_rows, int64_t nrows, i
       // (a runtime that cannot capture this sequence: the scan is launched directly, now and from here on)
       if (g) (void)hipGraphDestroy(g);
       (void)hipGetLastError(); h->graphs = 0;
-      return scan_launch(h, d_rows, nrows, own_rows, row_base, first_is_tape_start, d_workspace, workspace_bytes, d_bursts, max_bursts, d_nbursts, d_counts, d_events, event_capacity, stream); }
+      return scan_launch(h, a); }
    (void)hipGraphDestroy(g);
    rtfe_handle::GraphEnt &e = h->gcache[slot];
    if (e.exec) (void)hipGraphExecDestroy(e.exec);
@@ -1019,8 +1016,7 @@ extern "C" int rtfe_scan_exact(rtfe_handle *h, const int16_t *d_rows, int64_t nr
    const unsigned long long cap = (unsigned long long)(event_capacity / ((int64_t)h->dev.nparm * h->dev.ntrks));
    hipLaunchKernelGGL(k_setup_exact, dim3(1), dim3(1), 0, st, d_burst, scratch, (long long)reset_row, (long long)end_row,
                       cap > 0xffffffffull ? 0xffffffffull : cap);
-   const int nwalk = h->dev.nparm * h->dev.ntrks;
-   hipLaunchKernelGGL(k_decode, dim3(1), dim3(nwalk <= 64 ? 64 : (nwalk <= 128 ? 128 : 256)), h->lds_bytes, st, h->d_dev, d_rows, (long long)nrows,
+   hipLaunchKernelGGL(k_decode, dim3(1), dim3(decode_plan(h).walker_threads), h->lds_bytes, st, h->d_dev, d_rows, (long long)nrows,
                       (long long)row_base, d_burst, scratch, d_counts, d_events, parmset_mask, screen_off, 1, (int)kDecodeAll, (BurstCtl *)nullptr);
    return launch_check("rtfe_scan_exact"); }
 
