@@ -323,6 +323,33 @@ int rtfe_ww_detector_scan(rtfe_handle *h, const int16_t *d_rows, int64_t nrows, 
                           const void *d_state_in, void *d_state_out, size_t state_bytes, uint32_t *d_counts, rtfe_ww_event *d_events,
                           int64_t event_capacity, uint32_t *d_flags, void *stream);
 
+/* ---- CSV text -> int16 rows, on the device ----
+ * A logic-analyser export ("time, v0, v1, ..." lines) whose bytes lie in device memory becomes the rows rtfe_scan takes without visiting the host.
+ * The numbers are the host loader's (csrc/host/rt_csv.c: the reference's converter, src/csvtbin.c:619-716), bit for bit: its digit-by-digit float
+ * scanners, its peak, its quantiser and its clip count.  Handle-free and queued on `stream`; every pointer is device memory unless said otherwise.
+ * The ABI version did not move: additions only, and rtfe_kernel_count() stays what it was (these kernels are no spans of a scan).
+ * A WINDOW is a contiguous piece of the file's bytes: d_text 16-byte aligned and readable up to nbytes rounded up to 16, nbytes < 2^32.
+ *
+ * rtfe_csv_index: the lines of a window.  d_starts[i], i < lines: the offset of line i's first byte; d_starts[lines] == consumed, the offset behind the
+ *   last complete line (the next window starts there), so line i is [d_starts[i], d_starts[i + 1]), its '\n' included.  is_last: the window ends the
+ *   file, and the bytes behind its last '\n', if there are any, are a line too (fgets returns an unterminated last line, and nothing for an empty one).
+ *   longest: the longest line, '\n' included (at most 2^31 - 1 is reported).  d_starts holds starts_cap + 1 entries: a window with more lines than
+ *   starts_cap sets RTFE_CSV_STARTS_FULL, writes the entries that fit and nothing out of bounds - lines, consumed and longest are right all the same:
+ *   come back with lines entries.  d_scratch: rtfe_csv_index_scratch_bytes(nbytes), 16-byte aligned.
+ * rtfe_csv_peak: lines [first_line, first_line + nlines) of an indexed window - the time field skipped, then ntrks fields: *d_peak = max(*d_peak,
+ *   |field * scale|) (the caller starts it at 0; exact and independent of order).  rt_csv_survey's peak.
+ * rtfe_csv_parse: nkept lines first_line, first_line + step, ... of an indexed window -> d_rows[j * ntrks + (perm ? perm[k] : k)] = the code of line j's
+ *   field k (missing fields are 0); perm is HOST memory and may be NULL.  *d_clipped += the codes that met a rail (+-32767 included, as on the host).
+ *   ntrks outside 1 .. 19: -3, a perm entry outside 0 .. ntrks - 1: -4 (rt_csv_load's codes; rtfe_last_error says which). rt_csv_load's rows. */
+#define RTFE_CSV_STARTS_FULL 1
+typedef struct rtfe_csv_window { int64_t lines; int64_t consumed; uint32_t longest; uint32_t flags; } rtfe_csv_window;      /* 24 bytes */
+size_t rtfe_csv_index_scratch_bytes(uint64_t nbytes);
+int rtfe_csv_index(const void *d_text, uint64_t nbytes, int is_last, uint32_t *d_starts, int64_t starts_cap, void *d_scratch, size_t scratch_bytes,
+                   rtfe_csv_window *d_out, void *stream);
+int rtfe_csv_peak(const void *d_text, const uint32_t *d_starts, int64_t first_line, int64_t nlines, int ntrks, float scale, float *d_peak, void *stream);
+int rtfe_csv_parse(const void *d_text, const uint32_t *d_starts, int64_t first_line, int64_t step, int64_t nkept, int ntrks, const int *perm, int invert,
+                   float scale, float maxvolts, int16_t *d_rows, int64_t *d_clipped, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

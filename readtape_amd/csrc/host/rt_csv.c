@@ -46,7 +46,12 @@ static int next_line(FILE *f, char *line) {
    line[LINE_MAX_CHARS - 1] = 0;
    return 1; }
 
+double rt_csv_scan_time(const char *line) { return scan_f64(&line); }
+
 int rt_csv_survey(const char *path, int ntrks, float scale, int subsample, float maxvolts_given, struct rt_csv_info *out) {
+   return rt_csv_survey_n(path, ntrks, scale, subsample, maxvolts_given, PREREAD_ROWS, out); }
+
+int rt_csv_survey_n(const char *path, int ntrks, float scale, int subsample, float maxvolts_given, int64_t preread_rows, struct rt_csv_info *out) {
    char line[LINE_MAX_CHARS + 1];
    FILE *f = fopen(path, "r");
    if (!f) return -1;
@@ -57,7 +62,7 @@ int rt_csv_survey(const char *path, int ntrks, float scale, int subsample, float
    float peak = 0;
    int64_t n = 0;
    uint32_t tdelta = 0;
-   while (next_line(f, line) && ++n < PREREAD_ROWS) {
+   while (next_line(f, line) && ++n < preread_rows) {
       const char *p = line;
       const double t = scan_f64(&p);
       if (t_first < 0) { t_first = t; out->tstart_ns = (uint64_t)((t_first + 0.5e-9) * 1e9); }
@@ -68,7 +73,7 @@ int rt_csv_survey(const char *path, int ntrks, float scale, int subsample, float
          if (peak < v) peak = v; } }
    /* the rows of the whole file (the pre-read stops at a million) */
    int64_t rows = n;                                   /* (n counted the line on which the pre-read stopped, too) */
-   if (n >= PREREAD_ROWS) while (next_line(f, line)) ++rows;
+   if (n >= preread_rows) while (next_line(f, line)) ++rows;
    fclose(f);
    peak = ((float)(int)((peak + 0.55f) * 10.0f)) / 10.0f;
    if (subsample > 1) { out->tstart_ns += (uint64_t)(subsample - 1) * tdelta; tdelta *= (uint32_t)subsample; }

@@ -15,6 +15,10 @@ struct rt_csv_info {
 };
 /* first pass: period, start time, full scale (maxvolts_given = 0: derive it), row count */
 int rt_csv_survey(const char *path, int ntrks, float scale, int subsample, float maxvolts_given, struct rt_csv_info *out);
+/* ... with the pre-read's length given (rt_csv_survey: a million lines; the line on which it stops is counted but not surveyed) */
+int rt_csv_survey_n(const char *path, int ntrks, float scale, int subsample, float maxvolts_given, int64_t preread_rows, struct rt_csv_info *out);
+/* the timestamp in front of one line, as the survey reads it (the device path parses two of them on the host: the first and the last surveyed line's) */
+double rt_csv_scan_time(const char *line);
 /* second pass: rows[n][ntrks] int16 codes, column k of the file going to column perm[k] (NULL = identity); returns the rows written */
 int64_t rt_csv_load(const char *path, int ntrks, const int *perm, int invert, float scale, int subsample, float maxvolts,
                     int16_t *rows, int64_t capacity, int64_t *clipped);

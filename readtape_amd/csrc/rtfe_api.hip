@@ -23,6 +23,7 @@
 #include "rtfe_gain.hip"
 #include "rtfe_dense.hip"
 #include "rtfe_pack.hip"
+#include "rtfe_csv.hip"
 
 namespace rtfe {
 __global__ void k_setup_exact(rtfe_burst *burst, BurstScratch *scratch, long long reset_row, long long end_row,
@@ -1086,3 +1087,53 @@ extern "C" int rtfe_ww_detector_scan(rtfe_handle *h, const int16_t *d_rows, int6
                       (long long)first_row, (long long)nscan, (long long)seed_row0, k, (const rtfe_ww_dtrack *)d_state_in, (rtfe_ww_dtrack *)d_state_out,
                       d_counts, d_events, (long long)event_capacity, d_flags);
    return launch_check("rtfe_ww_detector_scan"); }
+
+// ---- CSV text -> int16 rows on the device (include/rt_frontend.h; kernels in rtfe_csv.hip) ----
+static uint32_t csv_blocks(uint64_t nbytes) { return (uint32_t)((nbytes + kCsvBlockBytes - 1) / kCsvBlockBytes); }
+extern "C" size_t rtfe_csv_index_scratch_bytes(uint64_t nbytes) { return (size_t)csv_blocks(nbytes) * 8 + 16; }
+
+extern "C" int rtfe_csv_index(const void *d_text, uint64_t nbytes, int is_last, uint32_t *d_starts, int64_t starts_cap, void *d_scratch, size_t scratch_bytes,
+                              rtfe_csv_window *d_out, void *stream) {
+   if (!d_text || !d_starts || !d_scratch || !d_out) return fail(-1, "rtfe_csv_index: null argument");
+   if (((uintptr_t)d_text & 15) != 0) return fail(-31, "rtfe_csv_index: d_text must be 16-byte aligned");
+   if (nbytes >= (1ull << 32)) return fail(-35, "rtfe_csv_index: a window of %llu bytes (shorter than 2^32)", (unsigned long long)nbytes);
+   if (starts_cap < 0) return fail(-34, "rtfe_csv_index: starts_cap %lld", (long long)starts_cap);
+   if (scratch_bytes < rtfe_csv_index_scratch_bytes(nbytes)) return fail(-32, "rtfe_csv_index: scratch too small");
+   hipStream_t st = (hipStream_t)stream;
+   const uint32_t nb = csv_blocks(nbytes);
+   uint32_t *cnt = reinterpret_cast<uint32_t *>(d_scratch), *last = cnt + nb;
+   const uint4 *text = reinterpret_cast<const uint4 *>(d_text);
+   if (nb) hipLaunchKernelGGL(k_csv_count, dim3(nb), dim3(256), 0, st, text, (uint32_t)nbytes, cnt, last);
+   hipLaunchKernelGGL(k_csv_scan, dim3(1), dim3(kCsvScanThreads), 0, st, nb, (uint32_t)nbytes, is_last != 0, cnt, last, d_starts, (long long)starts_cap, d_out);
+   if (nb) hipLaunchKernelGGL(k_csv_starts, dim3(nb), dim3(256), 0, st, text, (uint32_t)nbytes, (const uint32_t *)cnt, (const uint32_t *)last, d_starts, (long long)starts_cap, d_out);
+   return launch_check("rtfe_csv_index"); }
+
+extern "C" int rtfe_csv_peak(const void *d_text, const uint32_t *d_starts, int64_t first_line, int64_t nlines, int ntrks, float scale, float *d_peak, void *stream) {
+   if (!d_text || !d_starts || !d_peak) return fail(-1, "rtfe_csv_peak: null argument");
+   if (ntrks < 1 || ntrks > RTFE_MAXTRKS) return fail(-3, "rtfe_csv_peak: ntrks %d out of range", ntrks);
+   if (((uintptr_t)d_text & 15) != 0) return fail(-31, "rtfe_csv_peak: d_text must be 16-byte aligned");
+   if (first_line < 0 || nlines < 0 || first_line + nlines >= (1ll << 32)) return fail(-34, "rtfe_csv_peak: bad line range");
+   if (nlines == 0) return 0;
+   hipLaunchKernelGGL(k_csv_peak, dim3((unsigned)((nlines + kCsvWaveLines - 1) / kCsvWaveLines)), dim3(kCsvWaveLines), 0, (hipStream_t)stream,
+                      reinterpret_cast<const unsigned char *>(d_text), d_starts, (long long)first_line, (long long)nlines, ntrks, scale, d_peak);
+   return launch_check("rtfe_csv_peak"); }
+
+extern "C" int rtfe_csv_parse(const void *d_text, const uint32_t *d_starts, int64_t first_line, int64_t step, int64_t nkept, int ntrks, const int *perm, int invert,
+                              float scale, float maxvolts, int16_t *d_rows, int64_t *d_clipped, void *stream) {
+   if (!d_text || !d_starts || !d_rows || !d_clipped) return fail(-1, "rtfe_csv_parse: null argument");
+   if (ntrks < 1 || ntrks > RTFE_MAXTRKS) return fail(-3, "rtfe_csv_parse: ntrks %d out of range", ntrks);
+   if (perm) for (int k = 0; k < ntrks; ++k) if (perm[k] < 0 || perm[k] >= ntrks) return fail(-4, "rtfe_csv_parse: perm[%d] = %d out of range", k, perm[k]);
+   if (((uintptr_t)d_text & 15) != 0) return fail(-31, "rtfe_csv_parse: d_text must be 16-byte aligned");
+   if (first_line < 0 || step < 1 || nkept < 0 || first_line + (nkept ? (nkept - 1) * step + 1 : 0) >= (1ll << 32)) return fail(-34, "rtfe_csv_parse: bad line range");
+   if (nkept == 0) return 0;
+   CsvParseArgs a;
+   a.text = reinterpret_cast<const unsigned char *>(d_text); a.starts = d_starts;
+   a.first_line = first_line; a.step = step; a.nkept = nkept;
+   a.ntrks = ntrks; a.invert = invert != 0; a.scale = scale; a.maxvolts = maxvolts;
+   a.perm_lo = 0; a.perm_hi = 0;
+   for (int k = 0; k < ntrks; ++k) {
+      const unsigned long long c = (unsigned long long)(perm ? perm[k] : k);
+      if (k < 12) a.perm_lo |= c << (5 * k); else a.perm_hi |= c << (5 * (k - 12)); }
+   a.rows = d_rows; a.clipped = reinterpret_cast<unsigned long long *>(d_clipped);
+   hipLaunchKernelGGL(k_csv_parse, dim3((unsigned)((nkept + kCsvWaveLines - 1) / kCsvWaveLines)), dim3(kCsvWaveLines), 0, (hipStream_t)stream, a);
+   return launch_check("rtfe_csv_parse"); }

@@ -258,6 +258,12 @@ def _load_library(path=None):
     lib.rtfe_set_graphs.argtypes = [C.c_void_p, C.c_int]
     lib.rtfe_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
     lib.rtfe_reset_floor.argtypes = [C.c_void_p, C.c_void_p]
+    if hasattr(lib, "rtfe_csv_index"):                     # CSV text -> rows on the device (csvin.read_csv_device)
+        lib.rtfe_csv_index_scratch_bytes.argtypes = [C.c_uint64]; lib.rtfe_csv_index_scratch_bytes.restype = C.c_size_t
+        lib.rtfe_csv_index.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        lib.rtfe_csv_peak.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_float, C.c_void_p, C.c_void_p]
+        lib.rtfe_csv_parse.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_float, C.c_float,
+                                       C.c_void_p, C.c_void_p, C.c_void_p]
     if lib.rtfe_abi_version() != 6:
         raise RuntimeError("librtfe.so ABI mismatch")
     return lib
