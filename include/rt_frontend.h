@@ -350,6 +350,38 @@ int rtfe_csv_peak(const void *d_text, const uint32_t *d_starts, int64_t first_li
 int rtfe_csv_parse(const void *d_text, const uint32_t *d_starts, int64_t first_line, int64_t step, int64_t nkept, int ntrks, const int *perm, int invert,
                    float scale, float maxvolts, int16_t *d_rows, int64_t *d_clipped, void *stream);
 
+/* ---- int16 rows -> CSV text, on the device: the converter's -read (src/csvtbin.c:570-595) ----
+ * The mirror image of the block above: rows that are resident in device memory become the text the reference's `csvtbin -read` prints for them, byte for
+ * byte - "%12.8f, " of (double)t_ns / 1e9, then per column "%9.5f, " of the float32 value code / 32767 * maxvolts (negated if invert, plus k * stagger summed
+ * in float32), then '\n'; the last field keeps its ", ".  The two title lines are the caller's (csrc/host/rt_csvout.c writes them).  The host writer
+ * rt_csv_export_write (csrc/host/rt_csv.h) prints the same lines with fprintf; the kernels (csrc/rtfe_csvout.hip) make both fields in exact integer
+ * arithmetic.  Handle-free and queued on `stream`; every pointer is device memory unless said otherwise.  The ABI version did not move: additions only, and
+ * rtfe_kernel_count() stays what it was (these kernels are no spans of a scan).
+ * A WINDOW is rows [first_row, first_row + nrows) of the tape d_rows[.][ntrks] (d_rows points at row 0: a row's time is tstart_ns + row * tdelta_ns); its text
+ * is one contiguous piece at d_text (16-byte aligned, text_cap bytes), line after line from offset 0.
+ *
+ * rtfe_csv_format: the window's text.  *d_out: bytes = the length of the whole text, rows = nrows, longest = its longest line ('\n' included).  A text
+ *   longer than text_cap sets RTFE_CSV_TEXT_FULL: the first text_cap bytes are written, nothing at or behind d_text + text_cap, and bytes is right all the
+ *   same - come back with that much.  rtfe_csv_format_max_bytes(nrows, ntrks) always suffices.  d_scratch: rtfe_csv_format_scratch_bytes(nrows), 16-byte aligned.
+ *   a->perm is HOST memory and may be NULL: column k prints d_rows[.][perm[k]].
+ *   Two layouts, chosen here (rtfe_csv_format_path says which: 1 / 0, or the refusal): UNIFORM where every line provably has 14 + 11 ntrks + 1 bytes - the
+ *   window's last time below 1000 s and |maxvolts| 32768 / 32767 + (ntrks - 1) |stagger| below 99 -, one kernel; GENERAL otherwise, a length pass and a prefix
+ *   sum in front of it.
+ *   Refusals: ntrks outside 1 .. 19: -3; a perm entry outside 0 .. ntrks - 1: -4; d_text not 16-byte aligned: -31; scratch too small: -32; a negative row
+ *   range or more rows than a launch takes: -34; |maxvolts| 32768 / 32767 + (ntrks - 1) |stagger| not finite or not below 2^20 (the integer formatter's
+ *   domain): -46; the window's last time 2^49 ns (6.5 days) or more (the time field's proof): -47.  rtfe_last_error says which. */
+#define RTFE_CSV_TEXT_FULL 1
+typedef struct rtfe_csv_format_args {
+   int ntrks; int invert; float maxvolts; float stagger; uint64_t tstart_ns; uint32_t tdelta_ns;
+   const int *perm;                  /* host, may be NULL: column k prints rows[.][perm[k]] */
+} rtfe_csv_format_args;
+typedef struct rtfe_csv_text { uint64_t bytes; int64_t rows; uint32_t flags; uint32_t longest; } rtfe_csv_text;      /* 24 bytes */
+size_t rtfe_csv_format_max_bytes(int64_t nrows, int ntrks);       /* worst-case text of a window: 17 + 16 ntrks + 1 bytes a line */
+size_t rtfe_csv_format_scratch_bytes(int64_t nrows);
+int    rtfe_csv_format_path(int64_t first_row, int64_t nrows, const rtfe_csv_format_args *a);
+int    rtfe_csv_format(const int16_t *d_rows, int64_t first_row, int64_t nrows, const rtfe_csv_format_args *a,
+                       void *d_text, size_t text_cap, void *d_scratch, size_t scratch_bytes, rtfe_csv_text *d_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,6 +22,14 @@ double rt_csv_scan_time(const char *line);
 /* second pass: rows[n][ntrks] int16 codes, column k of the file going to column perm[k] (NULL = identity); returns the rows written */
 int64_t rt_csv_load(const char *path, int ntrks, const int *perm, int invert, float scale, int subsample, float maxvolts,
                     int16_t *rows, int64_t capacity, int64_t *clipped);
+
+/* ---- the other direction: rows -> the text of the converter's -read (src/csvtbin.c:523-596; rt_csvout.c) ---- */
+/* the rows [*first, *first + *count) that -skip / -starttime / -endtime / -stopaft leave of nrows rows (a value <= 0: not given) */
+int rt_csv_export_window(uint64_t tstart_ns, uint32_t tdelta_ns, int64_t nrows, int64_t skip, float starttime, float endtime, int64_t stopaft,
+                         int64_t *first, int64_t *count);
+/* the two title lines and those rows, by fprintf; column k prints rows[.][perm ? perm[k] : k].  Returns the bytes written, negative on failure */
+int64_t rt_csv_export_write(const char *path, const char *descr, int ntrks, const int *perm, int invert, float maxvolts, float stagger,
+                            uint64_t tstart_ns, uint32_t tdelta_ns, const int16_t *rows, int64_t first, int64_t count);
 #ifdef __cplusplus
 }
 #endif

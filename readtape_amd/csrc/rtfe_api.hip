@@ -24,6 +24,7 @@
 #include "rtfe_dense.hip"
 #include "rtfe_pack.hip"
 #include "rtfe_csv.hip"
+#include "rtfe_csvout.hip"
 
 namespace rtfe {
 __global__ void k_setup_exact(rtfe_burst *burst, BurstScratch *scratch, long long reset_row, long long end_row,
@@ -1137,3 +1138,61 @@ extern "C" int rtfe_csv_parse(const void *d_text, const uint32_t *d_starts, int6
    a.rows = d_rows; a.clipped = reinterpret_cast<unsigned long long *>(d_clipped);
    hipLaunchKernelGGL(k_csv_parse, dim3((unsigned)((nkept + kCsvWaveLines - 1) / kCsvWaveLines)), dim3(kCsvWaveLines), 0, (hipStream_t)stream, a);
    return launch_check("rtfe_csv_parse"); }
+
+// ---- int16 rows -> CSV text on the device (include/rt_frontend.h; kernels in rtfe_csvout.hip) ----
+// what the arguments admit: a refusal (negative), or whether every line of the window provably has the uniform length
+static int co_plan(const char *who, int64_t first_row, int64_t nrows, const rtfe_csv_format_args *a, bool *uniform) {
+   if (!a) return fail(-1, "%s: null argument", who);
+   if (a->ntrks < 1 || a->ntrks > RTFE_MAXTRKS) return fail(-3, "%s: ntrks %d out of range", who, a->ntrks);
+   if (a->perm) for (int k = 0; k < a->ntrks; ++k) if (a->perm[k] < 0 || a->perm[k] >= a->ntrks) return fail(-4, "%s: perm[%d] = %d out of range", who, k, a->perm[k]);
+   if (first_row < 0 || nrows < 0 || first_row > INT64_MAX - nrows) return fail(-34, "%s: bad row range", who);
+   const double bound = fabs((double)a->maxvolts) * 32768.0 / 32767.0 + (a->ntrks - 1) * fabs((double)a->stagger);
+   if (!(bound < 1048576.0)) return fail(-46, "%s: maxvolts %g with stagger %g over %d tracks is outside the formatter's domain (below 2^20 volts)", who, (double)a->maxvolts, (double)a->stagger, a->ntrks);
+   unsigned __int128 last = a->tstart_ns;
+   if (nrows > 0) last += (unsigned __int128)(uint64_t)(first_row + nrows - 1) * a->tdelta_ns;
+   if (nrows > 0 && last >= ((unsigned __int128)1 << 49)) return fail(-47, "%s: the window's last time is 2^49 ns or more", who);
+   // a time prints three digits in front of its point while it ROUNDS below 1000 s: t + 5 < 10^12 ns
+   *uniform = last + 5 < (unsigned __int128)1000000000000ull && bound < 99.0;
+   return 0; }
+
+extern "C" size_t rtfe_csv_format_max_bytes(int64_t nrows, int ntrks) { return nrows > 0 && ntrks > 0 ? (size_t)nrows * (size_t)co_max_line(ntrks) : 0; }
+// (a workgroup formats at least (kCoLds - 16) / co_max_line(19) = 50 rows)
+extern "C" size_t rtfe_csv_format_scratch_bytes(int64_t nrows) { return (size_t)((nrows > 0 ? nrows : 0) / co_lines_per_wg(co_max_line(RTFE_MAXTRKS)) + 1) * 8 + 16; }
+extern "C" int rtfe_csv_format_path(int64_t first_row, int64_t nrows, const rtfe_csv_format_args *a) {
+   bool uniform = false;
+   const int rc = co_plan("rtfe_csv_format_path", first_row, nrows, a, &uniform);
+   return rc ? rc : (uniform ? 1 : 0); }
+
+extern "C" int rtfe_csv_format(const int16_t *d_rows, int64_t first_row, int64_t nrows, const rtfe_csv_format_args *a, void *d_text, size_t text_cap,
+                               void *d_scratch, size_t scratch_bytes, rtfe_csv_text *d_out, void *stream) {
+   if (!d_rows || !a || !d_text || !d_scratch || !d_out) return fail(-1, "rtfe_csv_format: null argument");
+   bool uniform = false;
+   const int rc = co_plan("rtfe_csv_format", first_row, nrows, a, &uniform);
+   if (rc) return rc;
+   if (((uintptr_t)d_text & 15) != 0) return fail(-31, "rtfe_csv_format: d_text must be 16-byte aligned");
+   if (((uintptr_t)d_scratch & 7) != 0 || scratch_bytes < rtfe_csv_format_scratch_bytes(nrows)) return fail(-32, "rtfe_csv_format: scratch too small or misaligned");
+   hipStream_t st = (hipStream_t)stream;
+   CsvFormatArgs k;
+   k.rows = d_rows; k.first_row = first_row; k.nrows = nrows;
+   k.ntrks = a->ntrks; k.invert = a->invert != 0; k.maxvolts = a->maxvolts; k.stagger = a->stagger;
+   k.tstart = a->tstart_ns; k.tdelta = a->tdelta_ns;
+   k.perm_lo = k.perm_hi = 0;
+   for (int c = 0; c < a->ntrks; ++c) {
+      const unsigned long long col = (unsigned long long)(a->perm ? a->perm[c] : c);
+      if (c < 12) k.perm_lo |= col << (5 * c); else k.perm_hi |= col << (5 * (c - 12)); }
+   k.uniform_len = uniform ? (uint32_t)co_uniform_line(a->ntrks) : 0;
+   k.lines = co_lines_per_wg(uniform ? co_uniform_line(a->ntrks) : co_max_line(a->ntrks));
+   k.base = reinterpret_cast<const unsigned long long *>(d_scratch);
+   k.text = reinterpret_cast<unsigned char *>(d_text); k.text_cap = text_cap;
+   const int64_t nwg = (nrows + k.lines - 1) / k.lines;
+   if (nwg > 0x7fffffffll) return fail(-34, "rtfe_csv_format: %lld rows are more than a launch takes", (long long)nrows);
+   if (uniform) {
+      hipLaunchKernelGGL(k_csvout_total, dim3(1), dim3(1), 0, st, d_out, (unsigned long long)nrows * k.uniform_len, (long long)nrows, nrows ? k.uniform_len : 0u, (unsigned long long)text_cap);
+      if (nwg) hipLaunchKernelGGL(k_csvout_format<true>, dim3((unsigned)nwg), dim3(kCoWave), 0, st, k); }
+   else {
+      if (hipMemsetAsync(d_out, 0, sizeof(rtfe_csv_text), st) != hipSuccess) return fail(-30, "rtfe_csv_format: hipMemsetAsync failed");
+      unsigned long long *sums = reinterpret_cast<unsigned long long *>(d_scratch);
+      if (nwg) hipLaunchKernelGGL(k_csvout_len, dim3((unsigned)nwg), dim3(kCoWave), 0, st, k, sums, d_out);
+      hipLaunchKernelGGL(k_csvout_scan, dim3(1), dim3(kCoScanThreads), 0, st, (uint32_t)nwg, sums, (long long)nrows, (unsigned long long)text_cap, d_out);
+      if (nwg) hipLaunchKernelGGL(k_csvout_format<false>, dim3((unsigned)nwg), dim3(kCoWave), 0, st, k); }
+   return launch_check("rtfe_csv_format"); }
