@@ -394,10 +394,16 @@ def nrzi_tape(seed: int = 1, nblocks: int = 4, minlen: int = 64, maxlen: int = 5
 
 
 def pe_tape(seed: int = 1, nblocks: int = 3, minlen: int = 64, maxlen: int = 300,
-            gap_samples: int = 5000, **kw) -> Tape:
+            gap_samples: int = 5000, pre: int = 40, post: int = 40, marks_every: int = 0, **kw) -> Tape:
+    """pre, post: zero bits of every block's preamble and postamble; marks_every: a tape mark behind every so many blocks
+    (the defaults leave a seed's tape what it was)"""
     spec = pe_spec(seed=seed, **kw)
     rng = np.random.default_rng(seed + 2000)
-    items = [("block", p) for p in random_payloads(rng, nblocks, minlen, maxlen)]
+    items = []
+    for i, p in enumerate(random_payloads(rng, nblocks, minlen, maxlen)):
+        items.append(("block", p) if (pre, post) == (40, 40) else ("raw",) + pe_encode(p, spec.ntrks, pre=pre, post=post))
+        if marks_every and (i + 1) % marks_every == 0:
+            items.append(("mark",))
     return make_tape(spec, items, gap_samples=gap_samples)
 
 

@@ -319,6 +319,54 @@ def case_ww_rails(seed=56):
     return _clipped(synth.ww_tape(seed=seed, nblocks=4, minwords=3, maxwords=10, marks_every=2, gap_samples=700), 3)
 
 
+# ---- where a PE preamble ends (tests/pe_shapes.py): one recorded tape per named class; the emulator and GPU tests of the classes draw more
+def _pe_shapes_tape(cls, seed, **kw):
+    import pe_shapes
+    return pe_shapes.tape(cls, seed, **kw)["tape"]
+
+
+def case_pe_pre35(seed=61):
+    # 35 zero bits: the marker is peak 70, one short of "peakcount > 70" - the switch falls inside the data and the reference cannot read the blocks
+    return _pe_shapes_tape("P-length", seed, pres=(35, 35))
+
+
+def case_pe_pre36(seed=62):
+    # 36 zero bits: the marker is peak 72, the shortest preamble the reference reads
+    return _pe_shapes_tape("P-length", seed, pres=(36, 36))
+
+
+def case_pe_pre20(seed=63):
+    return _pe_shapes_tape("P-length", seed, pres=(20, 20))
+
+
+def case_pe_mark(seed=0):
+    # block, tape mark of 60 flux changes, block, tape mark of 72: the count passes 70 on a mark's six tracks with no one in sight
+    return _pe_shapes_tape("P-mark", seed, nitems=4)
+
+
+def case_pe_drop(seed=0):
+    # dropouts over peaks 60 .. 76, over peaks 4 .. 16 and over the marker, several tracks each
+    return _pe_shapes_tape("P-drop", seed, nblocks=3)
+
+
+def case_pe_clk(seed=1):
+    # one block with a parity error under eight sets whose t_clkwindow lies on, and one float32 either side of, the tape's own intervals (tstart_ns = 3e12: pe_shapes' note on equality)
+    return _pe_shapes_tape("P-clk", seed, nblocks=1)
+
+
+# pe_shapes.parms_text(pe_shapes.ladders(...)["both"]) of that tape (tests/test_emul_pe_shapes.py holds the two together)
+PE_CLK_PARMS = ("parms active, clk_window, clk_alpha, agc_window, agc_alpha, min_peak, clk_factor, pulse_adj, pkww_bitfrac, pkww_rise, midbit, z1pt, z2pt, id\n"
+                "{1, 0, 0.2, 5, 0.0, 0.0, 0.921599925, 0.4, 0.7, 0.1, 0.5, 1.45, 2.35, PRM}\n"
+                "{1, 0, 0.2, 5, 0.0, 0.0, 0.921600044, 0.4, 0.7, 0.1, 0.5, 1.45, 2.35, PRM}\n"
+                "{1, 0, 0.2, 5, 0.0, 0.0, 0.921600103, 0.4, 0.7, 0.1, 0.5, 1.45, 2.35, PRM}\n"
+                "{1, 0, 0.2, 5, 0.0, 0.0, 1.12639999, 0.4, 0.7, 0.1, 0.5, 1.45, 2.35, PRM}\n"
+                "{1, 0, 0.2, 5, 0.0, 0.0, 1.12640011, 0.4, 0.7, 0.1, 0.5, 1.45, 2.35, PRM}\n"
+                "{1, 0, 0.2, 5, 0.0, 0.0, 1.94559979, 0.4, 0.7, 0.1, 0.5, 1.45, 2.35, PRM}\n"
+                "{1, 0, 0.2, 5, 0.0, 0.0, 1.94560003, 0.4, 0.7, 0.1, 0.5, 1.45, 2.35, PRM}\n"
+                "{1, 0, 0.2, 5, 0.0, 0.0, 2, 0.4, 0.7, 0.1, 0.5, 1.45, 2.35, PRM}\n")
+case_pe_clk.parms_text = PE_CLK_PARMS
+
+
 # name -> (tape builder, reference options, oracle options); a builder's .parms_text, if any, is the NRZI/PE/GCR.parms file of the run
 CASES = {
     "nrzi9":        (case_nrzi9,      ["-nrzi"],                       []),
@@ -387,6 +435,13 @@ CASES = {
     "nrzi9_rails_invert_diffpk": (case_nrzi9_rails, ["-nrzi", "-invert", "-differentiate"], ["-invert", "-differentiate"]),
     "ww_rails_invert_neg": (case_ww_rails, ["-invert", "-fluxdir=neg"], ["-invert", "-fluxdir=neg"]),
     "ww_rails_invert_pos": (case_ww_rails, ["-invert", "-fluxdir=pos"], ["-invert", "-fluxdir=pos"]),
+    "pe_pre35":     (case_pe_pre35,   ["-pe"],                         []),
+    "pe_pre36":     (case_pe_pre36,   ["-pe"],                         []),
+    "pe_pre36_invert": (case_pe_pre36, ["-pe", "-invert"],             ["-invert"]),
+    "pe_pre20":     (case_pe_pre20,   ["-pe"],                         []),
+    "pe_mark":      (case_pe_mark,    ["-pe", "-m"],                   ["-m"]),
+    "pe_drop":      (case_pe_drop,    ["-pe"],                         []),
+    "pe_clk":       (case_pe_clk,     ["-pe", "-m"],                   ["-m"]),
 }
 # every reference run also gets: -v -tap -nolabels (SIMH .tap output, no IBM label handling);
 # "-nm" is added when "-m" is absent because the reference retries by default (src/readtape.c:511)

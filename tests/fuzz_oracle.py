@@ -13,6 +13,10 @@ ORA = os.path.join(ROOT, "oracle", "_build", "oracle_readtape")
 subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "all"], check=True)
 rng = np.random.default_rng(int(sys.argv[1]) if len(sys.argv) > 1 else 1)
 ntapes = int(sys.argv[2]) if len(sys.argv) > 2 else 20
+# sweeps numbered 5000 and up also draw a PE tape's preamble length and clk_factor (where a preamble ends: tests/pe_shapes.py) - from a generator of their own,
+# so that every earlier sweep keeps its tapes
+PE_NEW = (int(sys.argv[1]) if len(sys.argv) > 1 else 1) >= 5000
+rng_pe = np.random.default_rng((int(sys.argv[1]) if len(sys.argv) > 1 else 1) + 7_000_000)
 bad = 0
 LINES = lambda txt: [l.strip() for l in txt.splitlines() if l.startswith("wrote block") or "tapemark at" in l or "observed flux transitions" in l or "density was set to" in l or "average peak height is" in l]
 for i in range(ntapes):
@@ -49,7 +53,8 @@ for i in range(ntapes):
         if rng.random() < 0.12: tape.spec = dataclasses.replace(tape.spec, bpi=0.0)
         if rng.random() < 0.1: both("-subsample=2")
     elif kind == "pe":
-        tape = synth.pe_tape(seed=seed, nblocks=int(rng.integers(1, 5)), minlen=20, maxlen=int(rng.choice([100, 600])), gap_samples=3000, **kw)
+        pe_kw = dict(pre=int(rng_pe.choice([20, 33, 34, 35, 36, 37, 40, 90])), marks_every=int(rng_pe.choice([0, 0, 2]))) if PE_NEW else {}
+        tape = synth.pe_tape(seed=seed, nblocks=int(rng.integers(1, 5)), minlen=20, maxlen=int(rng.choice([100, 600])), gap_samples=3000, **pe_kw, **kw)
         ref.append("-pe")
         if rng.random() < 0.3: both("-m")
         r = rng.random()
@@ -74,8 +79,9 @@ for i in range(ntapes):
             rows2[a:b, t0] = (rows2[a:b, t0].astype(np.float32) * float(rng.choice([0.5, 0.25, 0.1, 0.0]))).astype(np.int16)
         tape = dataclasses.replace(tape, rows=rows2)
     parms_text = None
-    if rng.random() < 0.25:                                     # a <basename>.parms file with random front-end parameters (src/parmsets.c:337-372)
-        base = {"nrzi": [0, 0.2, None, None, None, 0, 0.3, None, None, 0.5, 1.45, 2.35], "pe": [0, 0.2, None, None, None, 1.5, 0.4, None, None, 0, 1.45, 2.35],
+    pe_cf = float(rng_pe.choice([1.0, 1.02, 1.05, 1.4, 1.5, 1.9, 1.95, 1.97, 1.99, 2.0])) if PE_NEW and kind == "pe" else 1.5
+    if (rng.random() < 0.25) | (pe_cf != 1.5):                  # a <basename>.parms file with random front-end parameters (src/parmsets.c:337-372)
+        base = {"nrzi": [0, 0.2, None, None, None, 0, 0.3, None, None, 0.5, 1.45, 2.35], "pe": [0, 0.2, None, None, None, pe_cf, 0.4, None, None, 0, 1.45, 2.35],
                 "gcr": [0, 0.015, None, None, None, 0, 0.3, None, None, 0, 1.45, 2.35]}[kind]
         spb = {"nrzi": 19.5, "pe": 19.5, "gcr": 13.8}[kind]
         lines = ["parms active, clk_window, clk_alpha, agc_window, agc_alpha, min_peak, clk_factor, pulse_adj, pkww_bitfrac, pkww_rise, midbit, z1pt, z2pt, id"]

@@ -61,6 +61,32 @@ def config_for(hdr, oracle_opts, parmset_ids=None, **kw):
     return frontend.FrontEndConfig.from_header(hdr, parmsets=sets, skew=skew, invert="-invert" in oracle_opts, **kw)
 
 
+def golden_config(g, **kw):
+    """the front end's configuration of a golden case (golden_util.load_case) - under the case's own parameter sets where it has a .parms text: the sets the
+    host library parses from it (all of them under -m, else the first)"""
+    opts = list(g["oracle_opts"])
+    if not g.get("parms_text"):
+        return config_for(g["hdr"], opts, **kw)
+    from readtape_amd import pipeline
+    arr = (pipeline._Parms * 15)()
+    n = pipeline._load_decode_lib().rt_parse_parms_text(g["hdr"].mode, g["parms_text"].encode(), arr)
+    assert n > 0, "bad parms text"
+    sets = pipeline.frontend_parmsets([arr[i] for i in range(n if "-m" in opts else 1)])
+    skew = next(([int(x) for x in o[6:].split(",")] for o in opts if o.startswith("-skew=")), None)
+    return frontend.FrontEndConfig.from_header(g["hdr"], parmsets=sets, skew=skew, invert="-invert" in opts, **kw)
+
+
+def golden_run(g, workdir, **kw):
+    """(the oracle's attempts, golden_config) of a golden case; the oracle reads a case's .parms text from a file"""
+    opts = list(g["oracle_opts"])
+    if g.get("parms_text"):
+        path = os.path.join(workdir, "t.parms")
+        with open(path, "w") as f:
+            f.write(g["parms_text"])
+        opts.append(f"-parms={path}")
+    return oracle_attempts(g["hdr"], g["rows"], opts, workdir), golden_config(g, **kw)
+
+
 def compare_attempt(fe, res, b, att, label=""):
     """Device events of (burst b, parmset) that were detected before the attempt ended vs the oracle's."""
     p = att["parmset"]

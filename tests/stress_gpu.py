@@ -48,6 +48,10 @@ def e2e_check(hdr, rows, opts, wd, parms_text=None):
 
 rng = np.random.default_rng(int(sys.argv[1]) if len(sys.argv) > 1 else 1)
 ntapes = int(sys.argv[2]) if len(sys.argv) > 2 else 16
+# sweeps numbered 5000 and up also draw a PE tape's preamble length and clk_factor (where a preamble ends: tests/pe_shapes.py) - from a generator of their own,
+# so that every earlier sweep keeps its tapes
+PE_NEW = (int(sys.argv[1]) if len(sys.argv) > 1 else 1) >= 5000
+rng_pe = np.random.default_rng((int(sys.argv[1]) if len(sys.argv) > 1 else 1) + 7_000_000)
 bad = 0
 for i in range(ntapes):
     kind = ["nrzi", "nrzi", "nrzi", "pe", "gcr"][int(rng.integers(0, 5))]
@@ -89,7 +93,8 @@ for i in range(ntapes):
         elif r < 0.38: opts.append("-even")
         elif r < 0.44: opts.append("-subsample=" + str(int(rng.choice([2, 3]))))
     elif kind == "pe":
-        tape = synth.pe_tape(seed=seed, nblocks=int(rng.integers(2, 5)), minlen=30, maxlen=int(rng.choice([200, 900])), gap_samples=3000, **kw)
+        pe_kw = dict(pre=int(rng_pe.choice([20, 33, 34, 35, 36, 37, 40, 90])), marks_every=int(rng_pe.choice([0, 0, 2]))) if PE_NEW else {}
+        tape = synth.pe_tape(seed=seed, nblocks=int(rng.integers(2, 5)), minlen=30, maxlen=int(rng.choice([200, 900])), gap_samples=3000, **pe_kw, **kw)
         if rng.random() < 0.3: opts.append("-m")
         elif rng.random() < 0.3: opts.append("-zeros")
     else:
@@ -105,8 +110,9 @@ for i in range(ntapes):
             rows2[a:b, t0] = (rows2[a:b, t0].astype(np.float32) * float(rng.choice([0.5, 0.25, 0.1, 0.0]))).astype(np.int16)
         tape = dataclasses.replace(tape, rows=rows2)
     parms_text = None
-    if rng.random() < 0.2:                                      # a .parms file with random front-end parameters (window 3..47 samples, either AGC flavour)
-        base = {"nrzi": [0, 0.2, None, None, None, 0, 0.3, None, None, 0.5, 1.45, 2.35], "pe": [0, 0.2, None, None, None, 1.5, 0.4, None, None, 0, 1.45, 2.35],
+    pe_cf = float(rng_pe.choice([1.0, 1.02, 1.05, 1.4, 1.5, 1.9, 1.95, 1.97, 1.99, 2.0])) if PE_NEW and kind == "pe" else 1.5
+    if (rng.random() < 0.2) | (pe_cf != 1.5):                   # a .parms file with random front-end parameters (window 3..47 samples, either AGC flavour)
+        base = {"nrzi": [0, 0.2, None, None, None, 0, 0.3, None, None, 0.5, 1.45, 2.35], "pe": [0, 0.2, None, None, None, pe_cf, 0.4, None, None, 0, 1.45, 2.35],
                 "gcr": [0, 0.015, None, None, None, 0, 0.3, None, None, 0, 1.45, 2.35]}[kind]
         spb = {"nrzi": 19.5, "pe": 19.5, "gcr": 13.8}[kind]
         lines = ["parms active, clk_window, clk_alpha, agc_window, agc_alpha, min_peak, clk_factor, pulse_adj, pkww_bitfrac, pkww_rise, midbit, z1pt, z2pt, id"]

@@ -9,7 +9,8 @@ from golden_util import load_case
 from readtape_amd import frontend, pipeline
 
 CASES = ["nrzi9", "nrzi9_m", "nrzi9_correct", "nrzi7", "nrzi9_skew", "nrzi9_invert", "nrzi9_sub2", "pe", "pe_m", "nrzi9_zeros", "pe_zeros", "gcr", "gcr_m", "gcr_zeros", "gcr_errs", "gcr_correct", "nrzi9_deskew", "nrzi9_deskew_long", "nrzi7_deskew_restart", "gcr_deskew", "nrzi9_nobpi", "nrzi9_nobpi_short", "nrzi9_diffz", "pe_diffz", "gcr_diffz", "nrzi9_diffpk", "nrzi9_diffpk_clean", "nrzi9_diffpk_skew", "gcr_diffpk", "pe_diffpk", "nrzi9_cut", "nrzi9_cut_zeros", "noise_only", "tiny", "nrzi9_nobpi_deskew", "nrzi7_order", "pe_order", "gcr_order_m", "nrzi7_order_ignored"]
-EMUL_CASES = ["nrzi9", "nrzi9_m", "nrzi9_skew", "nrzi9_sub2", "pe", "nrzi9_zeros", "pe_zeros", "gcr", "gcr_zeros", "gcr_correct", "nrzi9_deskew", "nrzi7_deskew_restart", "nrzi9_nobpi_short", "nrzi9_diffz", "pe_diffz", "gcr_diffz", "nrzi9_diffpk", "nrzi9_cut", "nrzi9_cut_zeros", "noise_only", "tiny", "nrzi7_order", "pe_order", "nrzi7_order_ignored"]     # the thread emulation is slow: a subset here, all on the GPU
+EMUL_CASES = ["nrzi9", "nrzi9_m", "nrzi9_skew", "nrzi9_sub2", "pe", "nrzi9_zeros", "pe_zeros", "gcr", "gcr_zeros", "gcr_correct", "nrzi9_deskew", "nrzi7_deskew_restart", "nrzi9_nobpi_short", "nrzi9_diffz", "pe_diffz", "gcr_diffz", "nrzi9_diffpk", "nrzi9_cut", "nrzi9_cut_zeros", "noise_only", "tiny", "nrzi7_order", "pe_order", "nrzi7_order_ignored",
+              "pe_pre35", "pe_pre36", "pe_pre36_invert", "pe_pre20", "pe_mark", "pe_drop", "pe_clk"]     # the thread emulation is slow: a subset here, all on the GPU
 
 
 def decode_case(g, tmp_path, fe_factory):
@@ -45,7 +46,8 @@ def test_tap_bytes_match_reference(name, tmp_path):
     assert not stats["event_diffs"], stats["event_diffs"]
 
 
-@pytest.mark.parametrize("name", ["pe", "pe_m", "gcr", "gcr_m", "gcr_correct", "gcr_deskew", "pe_order", "gcr_order_m", "nrzi9", "nrzi9_m", "nrzi9_skew"])
+@pytest.mark.parametrize("name", ["pe", "pe_m", "gcr", "gcr_m", "gcr_correct", "gcr_deskew", "pe_order", "gcr_order_m", "nrzi9", "nrzi9_m", "nrzi9_skew",
+                                  "pe_pre35", "pe_pre36", "pe_pre36_invert", "pe_pre20", "pe_mark", "pe_drop", "pe_clk"])
 def test_tap_bytes_match_reference_on_the_dense_path(name, tmp_path, monkeypatch):
     """rtfe_dense.hip (k_dseg + k_dchain; opt-in) end to end: the reference's .tap, its transitions and its block lines.  The NRZI cases take
     it by force (the peak path off)."""

@@ -5,12 +5,13 @@ import numpy as np
 import pytest
 
 from golden_util import load_case
-from parity_util import check_tape, config_for, oracle_attempts
+from parity_util import check_tape, config_for, golden_config, golden_run, oracle_attempts
 from readtape_amd import frontend, synth
 
 pytestmark = pytest.mark.gpu
 
-PEAK_CASES = ["nrzi9", "nrzi9_m", "nrzi7", "nrzi9_skew", "nrzi9_invert", "pe", "pe_m", "gcr", "gcr_m", "nrzi7_order", "pe_order", "gcr_order_m", "nrzi7_order_ignored"]
+PEAK_CASES = ["nrzi9", "nrzi9_m", "nrzi7", "nrzi9_skew", "nrzi9_invert", "pe", "pe_m", "gcr", "gcr_m", "nrzi7_order", "pe_order", "gcr_order_m", "nrzi7_order_ignored",
+              "pe_pre35", "pe_pre36", "pe_pre36_invert", "pe_pre20", "pe_mark", "pe_drop", "pe_clk"]      # (where a PE preamble ends: tests/pe_shapes.py)
 
 
 @pytest.fixture(scope="module")
@@ -23,8 +24,8 @@ def gpu():
 @pytest.mark.parametrize("name", PEAK_CASES)
 def test_golden_tapes(name, tmp_path, gpu):
     g = load_case(name)
-    att = oracle_attempts(g["hdr"], g["rows"], g["oracle_opts"], str(tmp_path))
-    fe = frontend.FrontEnd(config_for(g["hdr"], g["oracle_opts"]))
+    att, cfg = golden_run(g, str(tmp_path))
+    fe = frontend.FrontEnd(cfg)
     msgs, stats = check_tape(fe, g["hdr"], g["rows"], att)
     assert not msgs, "\n".join(msgs[:12])
     assert stats["events"] > 0
@@ -209,7 +210,8 @@ def test_large_tape_properties(gpu):
         assert got.shape == ref.shape and (got == ref).all(), f"copy {j}"
 
 
-@pytest.mark.parametrize("name", ["nrzi9", "nrzi9_m", "nrzi9_correct", "nrzi7", "nrzi9_skew", "nrzi9_invert", "nrzi9_sub2", "pe", "pe_m", "nrzi9_zeros", "pe_zeros", "gcr", "gcr_m", "gcr_zeros", "gcr_errs", "gcr_correct", "nrzi9_deskew", "nrzi9_deskew_long", "nrzi7_deskew_restart", "gcr_deskew", "nrzi9_nobpi", "nrzi9_nobpi_short", "nrzi9_diffz", "pe_diffz", "gcr_diffz", "nrzi9_diffpk", "nrzi9_diffpk_clean", "nrzi9_diffpk_skew", "gcr_diffpk", "pe_diffpk", "nrzi9_cut", "nrzi9_cut_zeros", "noise_only", "tiny", "nrzi9_nobpi_deskew", "nrzi7_order", "pe_order", "gcr_order_m", "nrzi7_order_ignored"])
+@pytest.mark.parametrize("name", ["nrzi9", "nrzi9_m", "nrzi9_correct", "nrzi7", "nrzi9_skew", "nrzi9_invert", "nrzi9_sub2", "pe", "pe_m", "nrzi9_zeros", "pe_zeros", "gcr", "gcr_m", "gcr_zeros", "gcr_errs", "gcr_correct", "nrzi9_deskew", "nrzi9_deskew_long", "nrzi7_deskew_restart", "gcr_deskew", "nrzi9_nobpi", "nrzi9_nobpi_short", "nrzi9_diffz", "pe_diffz", "gcr_diffz", "nrzi9_diffpk", "nrzi9_diffpk_clean", "nrzi9_diffpk_skew", "gcr_diffpk", "pe_diffpk", "nrzi9_cut", "nrzi9_cut_zeros", "noise_only", "tiny", "nrzi9_nobpi_deskew", "nrzi7_order", "pe_order", "gcr_order_m", "nrzi7_order_ignored",
+                                  "pe_pre35", "pe_pre36", "pe_pre36_invert", "pe_pre20", "pe_mark", "pe_drop", "pe_clk"])
 def test_end_to_end_tap_bytes_match_reference(name, tmp_path, gpu):
     """GPU front end -> event replay -> block decoders -> SIMH .tap == the unmodified reference's .tap (golden)."""
     from test_emul_replay import decode_case
@@ -271,7 +273,7 @@ def test_peak_record_path_equals_the_sample_path(name, gpu, monkeypatch):
     table and, per (burst, parameter set, track), the same events byte for byte - also behind the block ends, where no oracle
     attempt looks."""
     g = load_case(name)
-    cfg = config_for(g["hdr"], g["oracle_opts"])
+    cfg = golden_config(g)
     res = []
     for pp in ("0", "1"):
         monkeypatch.setenv("RTFE_PEAK_PATH", pp)
@@ -623,7 +625,8 @@ def test_sample_rates_and_the_lean_sift_kernels(tdelta_ns, ntrks, tmp_path, gpu)
     assert stats["events"] > 5000 and st["redone"] == 0 and st["parallel"] > 0, (stats, st)
 
 
-DENSE_GPU_CASES = ["pe", "pe_m", "gcr", "gcr_m", "gcr_errs", "gcr_deskew", "pe_order", "gcr_order_m", "nrzi9", "nrzi9_m", "nrzi9_skew", "nrzi9_invert", "nrzi7"]
+DENSE_GPU_CASES = ["pe", "pe_m", "gcr", "gcr_m", "gcr_errs", "gcr_deskew", "pe_order", "gcr_order_m", "nrzi9", "nrzi9_m", "nrzi9_skew", "nrzi9_invert", "nrzi7",
+                   "pe_pre35", "pe_pre36", "pe_pre36_invert", "pe_pre20", "pe_mark", "pe_drop", "pe_clk"]
 
 
 @pytest.mark.parametrize("name", DENSE_GPU_CASES)
@@ -635,8 +638,8 @@ def test_dense_path_against_the_oracle_and_the_reference(name, tmp_path, gpu, mo
     monkeypatch.setenv("RTFE_PEAK_PATH", "0")
     g = load_case(name)
     if "-deskew" not in g["oracle_opts"]:
-        att = oracle_attempts(g["hdr"], g["rows"], g["oracle_opts"], str(tmp_path))
-        fe = frontend.FrontEnd(config_for(g["hdr"], g["oracle_opts"]))
+        att, cfg = golden_run(g, str(tmp_path))
+        fe = frontend.FrontEnd(cfg)
         msgs, stats = check_tape(fe, g["hdr"], g["rows"], att)
         assert not msgs, "\n".join(msgs[:12])
         assert stats["events"] > 0

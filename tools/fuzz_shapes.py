@@ -14,6 +14,9 @@ writes such shapes over peaks of a clean NRZI tape - every sample of the window 
   python tools/fuzz_shapes.py [--gpu] --seams [seed0 [ntapes]]             (the amplitude shapes ON the seams of the peak and dense paths: tests/seam_shapes.py's tapes, every event field
                                                                             against the oracle, two scans a handle; a line per tape with what its shapes lay across and - on the
                                                                             emulator - what its segments met (seg_shapes:); stops at the first mismatch or failure)
+  python tools/fuzz_shapes.py [--gpu] --pe [seed0 [ntapes]]                (where a PE preamble ends: tests/pe_shapes.py's classes - a draw is a class, a seed, -invert, a -skew= list,
+                                                                            -m and a path - every event field against the oracle, two scans a handle; a line per tape with what
+                                                                            the oracle says it contains (classes_met) and the totals at the end; stops at the first mismatch or failure)
 """
 import os
 import sys
@@ -48,6 +51,8 @@ def main():
         return rails_main(make, seed0, ntapes)
     if "--seams" in sys.argv:
         return seams_main(make, gpu, seed0, ntapes)
+    if "--pe" in sys.argv:
+        return pe_main(make, seed0, ntapes)
     bad = 0
     for seed in range(seed0, seed0 + ntapes):
         d = draw(seed)
@@ -210,6 +215,48 @@ def seams_main(make, gpu, seed0, ntapes):
               + " ".join(f"{c} {cov.get(c, 0)}" for c in ss.SHAPES + (ss.PEAK_SEAMS if peak else ss.DENSE_SEAMS))
               + (" | " + " ".join(f"{k} {v // n}" for k, v in seg.items()) if n else ""), flush=True)
     print(f"FAILURES 0 ({nfast} of {ntapes} tapes on the fast paths)")
+    return 0
+
+
+def pe_main(make, seed0, ntapes):
+    """tests/pe_util.py's check of one drawn tape per seed (P-clk: one per ladder; P-time: one per start time); the first tape that fails ends the run (no retries)"""
+    import pe_shapes as ps
+    import pe_util as pu
+    keys = ("tracks", "sw_71_72", "sw_later", "sw_data", "sw_never", "never_past70", "marker_le70", "height_low", "near_1", "near_4", "equal")
+    grand, per_cls, per_path, nev = dict.fromkeys(keys + ("f32_intervals",), 0), {}, {}, 0
+    for seed in range(seed0, seed0 + ntapes):
+        d = ps.draw(seed)
+        for k in pu.KNOB_NAMES:
+            os.environ.pop(k, None)
+        os.environ.update(ps.PATHS[d["path"]])
+        try:
+            tapes = pu.tapes_of(d["cls"], seed, d["m"], d["invert"], d["skew"])
+            pu._cache.clear()
+            tot, ev = dict.fromkeys(keys + ("f32_intervals",), 0), 0
+            for label, tp, att, win in tapes:
+                met = ps.classes_met(tp["hdr"], att, win)
+                for k, v in ps.totals(met).items():
+                    if k in tot:
+                        tot[k] += v
+                tot["f32_intervals"] += ps.float32_intervals(met)
+                stats, fe = pu.check(make, tp, att, label=label)
+                ev += stats["events"]
+            fail = None
+        except Exception as e:                                   # a mismatch (AssertionError) or a failure of the front end
+            fail = f"{type(e).__name__}: {str(e)[:2000]}"
+        if fail:
+            print(f"FAIL seed {seed} {d}: {fail}", flush=True)
+            print("FAILURES 1 (stopped at the first)")
+            return 1
+        for k, v in tot.items():
+            grand[k] += v
+        per_cls[d["cls"]] = per_cls.get(d["cls"], 0) + 1
+        per_path[d["path"]] = per_path.get(d["path"], 0) + 1
+        nev += ev
+        print(f"ok seed {seed} {d} tapes {len(tapes)} events {ev} | " + " ".join(f"{k} {v}" for k, v in tot.items()), flush=True)
+    print("classes_met totals: " + " ".join(f"{k} {v}" for k, v in grand.items()))
+    print("draws per class: " + " ".join(f"{k} {v}" for k, v in sorted(per_cls.items())) + " | per path: " + " ".join(f"{k} {v}" for k, v in sorted(per_path.items())))
+    print(f"FAILURES 0 ({ntapes} draws, {nev} events compared)")
     return 0
 
 
