@@ -340,7 +340,13 @@ int rtfe_ww_detector_scan(rtfe_handle *h, const int16_t *d_rows, int64_t nrows, 
  *   |field * scale|) (the caller starts it at 0; exact and independent of order).  rt_csv_survey's peak.
  * rtfe_csv_parse: nkept lines first_line, first_line + step, ... of an indexed window -> d_rows[j * ntrks + (perm ? perm[k] : k)] = the code of line j's
  *   field k (missing fields are 0); perm is HOST memory and may be NULL.  *d_clipped += the codes that met a rail (+-32767 included, as on the host).
- *   ntrks outside 1 .. 19: -3, a perm entry outside 0 .. ntrks - 1: -4 (rt_csv_load's codes; rtfe_last_error says which). rt_csv_load's rows. */
+ *   ntrks outside 1 .. 19: -3, a perm entry outside 0 .. ntrks - 1: -4 (rt_csv_load's codes; rtfe_last_error says which). rt_csv_load's rows.
+ * rtfe_csv_graph: the converter's -graph and the peak its -redo needs (src/csvtbin.c:704-706, 719-722, 732).  The kept lines are rtfe_csv_parse's
+ *   (first_line, step, nkept); kept line j is sample first_sample + j of the pass (0-based), and for bins below nbins
+ *   d_bins[(first_sample + j) / graphbin] = max(its old value, max_k |field_k * scale| of the line); *d_peak (may be NULL) = max(*d_peak, the same over all
+ *   lines).  Non-negative floats compared as their bit patterns: exact and independent of order, so calls for different windows of a file may meet in one
+ *   bin.  The caller zeroes both; nothing is written at or behind d_bins + nbins (nbins 0: d_bins may be NULL).  Refusals: rtfe_csv_parse's, and -34 for
+ *   graphbin < 1, nbins < 0, first_sample < 0.  The sign flip of -invert does not change a magnitude, and -order= only moves columns: neither is an argument. */
 #define RTFE_CSV_STARTS_FULL 1
 typedef struct rtfe_csv_window { int64_t lines; int64_t consumed; uint32_t longest; uint32_t flags; } rtfe_csv_window;      /* 24 bytes */
 size_t rtfe_csv_index_scratch_bytes(uint64_t nbytes);
@@ -349,6 +355,8 @@ int rtfe_csv_index(const void *d_text, uint64_t nbytes, int is_last, uint32_t *d
 int rtfe_csv_peak(const void *d_text, const uint32_t *d_starts, int64_t first_line, int64_t nlines, int ntrks, float scale, float *d_peak, void *stream);
 int rtfe_csv_parse(const void *d_text, const uint32_t *d_starts, int64_t first_line, int64_t step, int64_t nkept, int ntrks, const int *perm, int invert,
                    float scale, float maxvolts, int16_t *d_rows, int64_t *d_clipped, void *stream);
+int rtfe_csv_graph(const void *d_text, const uint32_t *d_starts, int64_t first_line, int64_t step, int64_t nkept, int ntrks, float scale,
+                   int64_t first_sample, int64_t graphbin, float *d_bins, int64_t nbins, float *d_peak, void *stream);
 
 /* ---- int16 rows -> CSV text, on the device: the converter's -read (src/csvtbin.c:570-595) ----
  * The mirror image of the block above: rows that are resident in device memory become the text the reference's `csvtbin -read` prints for them, byte for

@@ -23,6 +23,36 @@ double rt_csv_scan_time(const char *line);
 int64_t rt_csv_load(const char *path, int ntrks, const int *perm, int invert, float scale, int subsample, float maxvolts,
                     int16_t *rows, int64_t capacity, int64_t *clipped);
 
+/* ---- the converter's window options, -graph and -redo (src/csvtbin.c:364-376, 661-747) ---- */
+enum { RT_CSV_ENDED_FILE = 0, RT_CSV_ENDED_STOPAFT = 1, RT_CSV_ENDED_ENDTIME = 2 };      /* how a pass ended */
+struct rt_csv_window {
+   int64_t skipped;         /* K: raw data lines the skipping loop drops */
+   int64_t first_line;      /* the raw data line (0 = the file's third line) of the first sample: K + subsample - 1 */
+   int64_t count;           /* samples written; sample j is raw data line first_line + j * subsample */
+   int     ended;           /* RT_CSV_ENDED_* */
+};
+/* the samples that -skip / -starttime / -endtime / -stopaft leave of a file of data_lines raw data lines (a value <= 0: not given); tstart_ns / tdelta_ns
+ * are the survey's, after its -subsample adjustment.  -5: the file ends inside the skip */
+int rt_csv_convert_window(uint64_t tstart_ns, uint32_t tdelta_ns, int64_t data_lines, int subsample, int64_t skip, float starttime, float endtime,
+                          int64_t stopaft, struct rt_csv_window *out);
+uint64_t rt_csv_seconds_ns(float seconds);            /* an option's seconds as the converter takes them */
+float rt_csv_redo_maxvolts(float newmax);             /* -redo's full scale for the largest magnitude of the first pass */
+struct rt_csv_pass_opts {
+   int ntrks; const int *perm; int invert; float scale; int subsample; float maxvolts;
+   int64_t skip; float starttime, endtime; int64_t stopaft; int64_t graphbin;      /* <= 0: not given */
+   uint64_t tstart_ns; uint32_t tdelta_ns;
+};
+struct rt_csv_pass {
+   int64_t skipped, samples, too_big, too_small, graph_lines;
+   int     ended;           /* RT_CSV_ENDED_* */
+   float   newmax;          /* the largest |sample| in volts: what -redo sizes the second pass by */
+};
+/* one pass over the file into whatever sinks are given (NULL: not wanted): rows in memory, a .tbin file, a graph file, the graph as numbers */
+int rt_csv_convert_pass(const char *csv_path, const struct rt_csv_pass_opts *o, int16_t *rows, int64_t capacity, const char *tbin_path, const void *header,
+                        int header_bytes, const char *graph_path, int64_t *graph_at, float *graph_max, int64_t graph_cap, struct rt_csv_pass *res);
+/* "<(i + 1) * graphbin>, <%f of bins[i]>" per bin: the graph file from maxima made elsewhere (rtfe_csv_graph) */
+int rt_csv_graph_write(const char *graph_path, int64_t graphbin, const float *bins, int64_t nbins);
+
 /* ---- the other direction: rows -> the text of the converter's -read (src/csvtbin.c:523-596; rt_csvout.c) ---- */
 /* the rows [*first, *first + *count) that -skip / -starttime / -endtime / -stopaft leave of nrows rows (a value <= 0: not given) */
 int rt_csv_export_window(uint64_t tstart_ns, uint32_t tdelta_ns, int64_t nrows, int64_t skip, float starttime, float endtime, int64_t stopaft,

@@ -1139,6 +1139,25 @@ extern "C" int rtfe_csv_parse(const void *d_text, const uint32_t *d_starts, int6
    hipLaunchKernelGGL(k_csv_parse, dim3((unsigned)((nkept + kCsvWaveLines - 1) / kCsvWaveLines)), dim3(kCsvWaveLines), 0, (hipStream_t)stream, a);
    return launch_check("rtfe_csv_parse"); }
 
+extern "C" int rtfe_csv_graph(const void *d_text, const uint32_t *d_starts, int64_t first_line, int64_t step, int64_t nkept, int ntrks, float scale,
+                              int64_t first_sample, int64_t graphbin, float *d_bins, int64_t nbins, float *d_peak, void *stream) {
+   if (!d_text || !d_starts || (!d_bins && nbins > 0)) return fail(-1, "rtfe_csv_graph: null argument");
+   if (ntrks < 1 || ntrks > RTFE_MAXTRKS) return fail(-3, "rtfe_csv_graph: ntrks %d out of range", ntrks);
+   if (((uintptr_t)d_text & 15) != 0) return fail(-31, "rtfe_csv_graph: d_text must be 16-byte aligned");
+   if (first_line < 0 || step < 1 || nkept < 0 || first_line + (nkept ? (nkept - 1) * step + 1 : 0) >= (1ll << 32)) return fail(-34, "rtfe_csv_graph: bad line range");
+   if (graphbin < 1) return fail(-34, "rtfe_csv_graph: graphbin %lld (samples per bin: at least 1)", (long long)graphbin);
+   if (nbins < 0) return fail(-34, "rtfe_csv_graph: nbins %lld", (long long)nbins);
+   if (first_sample < 0 || first_sample >= (1ll << 62)) return fail(-34, "rtfe_csv_graph: first_sample %lld", (long long)first_sample);
+   if (nkept == 0 || (nbins == 0 && !d_peak)) return 0;
+   CsvGraphArgs a;
+   a.text = reinterpret_cast<const unsigned char *>(d_text); a.starts = d_starts;
+   a.first_line = first_line; a.step = step; a.nkept = nkept;
+   a.ntrks = ntrks; a.scale = scale;
+   a.first_sample = first_sample; a.graphbin = graphbin; a.nbins = nbins;
+   a.bins = reinterpret_cast<int *>(d_bins); a.peak = reinterpret_cast<int *>(d_peak);
+   hipLaunchKernelGGL(k_csv_graph, dim3((unsigned)((nkept + kCsvWaveLines - 1) / kCsvWaveLines)), dim3(kCsvWaveLines), 0, (hipStream_t)stream, a);
+   return launch_check("rtfe_csv_graph"); }
+
 // ---- int16 rows -> CSV text on the device (include/rt_frontend.h; kernels in rtfe_csvout.hip) ----
 // what the arguments admit: a refusal (negative), or whether every line of the window provably has the uniform length
 static int co_plan(const char *who, int64_t first_row, int64_t nrows, const rtfe_csv_format_args *a, bool *uniform) {

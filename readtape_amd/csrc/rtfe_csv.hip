@@ -9,6 +9,7 @@
 //   k_csv_starts  the blocks again: starts[i] = the offset of line i's first byte; the longest line
 //   k_csv_peak    a lane per surveyed line: max |v * scale| (rt_csv_survey's peak)
 //   k_csv_parse   a lane per kept line: the line's int16 codes (rt_csv_load's row)
+//   k_csv_graph   a lane per kept line: max |v * scale| into the bin its sample number falls in (the converter's -graph) and into the pass's peak (-redo)
 // A line ends behind its '\n'; its end bounds the scanners the way the terminating NUL of the host's line buffer does.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -235,5 +236,48 @@ __global__ void __launch_bounds__(kCsvWaveLines) k_csv_parse(const CsvParseArgs 
       clips = sp.lds ? csv_line_row(reinterpret_cast<const unsigned char *>(s_text), p - sp.a0, e - sp.a0, a, o) : csv_line_row(a.text, p, e, a, o); }
    const int wc = csv_wave_sum(clips);
    if ((threadIdx.x & 63) == 0 && wc > 0) atomicAdd(a.clipped, (unsigned long long)wc); }
+
+struct CsvGraphArgs {
+   const unsigned char *text; const uint32_t *starts;
+   long long first_line, step, nkept;
+   int ntrks; float scale;
+   long long first_sample, graphbin, nbins;
+   int *bins, *peak;                          // non-negative floats, kept and compared as their bit patterns (k_csv_peak's argument)
+};
+
+// The converter's -graph (src/csvtbin.c:704-706, 719-722): kept line j is sample first_sample + j of the pass, and bins[that / graphbin] takes the line's
+// max_k |field_k * scale|.  A wave's 64 samples are consecutive, so their bins ascend: where the first and the last agree (always, but for one wave per
+// bin, once graphbin >= 64) the wave's maximum goes out in one atomic; otherwise a segmented scan leaves each run's maximum in its last lane.
+__global__ void __launch_bounds__(kCsvWaveLines) k_csv_graph(const CsvGraphArgs a) {
+   __shared__ uint4 s_text[kCsvLdsBudget / 16];
+   const int lane = threadIdx.x & 63;
+   const long long j0 = (long long)blockIdx.x * kCsvWaveLines, j = j0 + lane;
+   const CsvSpan sp = csv_stage(a.text, a.starts, a.first_line, a.step, a.nkept, s_text);
+   float v = 0;
+   if (j < a.nkept) {
+      const long long line = a.first_line + j * a.step;
+      const uint32_t p = a.starts[line], e = a.starts[line + 1];
+      v = sp.lds ? csv_line_peak(reinterpret_cast<const unsigned char *>(s_text), p - sp.a0, e - sp.a0, a.ntrks, a.scale) : csv_line_peak(a.text, p, e, a.ntrks, a.scale); }
+   int bits = (int)__float_as_uint(v);
+   const int wm = csv_wave_max(bits);
+   if (a.peak && lane == 0 && wm > 0) atomicMax(a.peak, wm);
+   // wave-uniform: the bins of the wave's first and last sample
+   const long long jl = (j0 + kCsvWaveLines < a.nkept ? j0 + kCsvWaveLines : a.nkept) - 1;
+   const long long b0 = (a.first_sample + j0) / a.graphbin, b1 = (a.first_sample + jl) / a.graphbin;
+   if (b0 >= a.nbins) return;
+   if (b0 == b1) {
+      if (lane == 0 && wm > 0) atomicMax(a.bins + b0, wm);
+      return; }
+   // the lane's bin relative to b0 (r0 < graphbin, and r0 + 63 >= graphbin here); -1 for a lane without a line
+   const long long r0 = a.first_sample + j0 - b0 * a.graphbin;
+   int key = a.graphbin >= kCsvWaveLines ? (int)(r0 + lane >= a.graphbin) : (int)(((uint32_t)r0 + (uint32_t)lane) / (uint32_t)a.graphbin);
+   if (j >= a.nkept) key = -1;
+   for (int m = 1; m < kCsvWaveLines; m <<= 1) {
+      const int src = lane >= m ? lane - m : lane;
+      const int ob = __shfl(bits, src), ok = __shfl(key, src);
+      if (lane >= m && ok == key && ob > bits) bits = ob; }
+   const int next = __shfl(key, lane < kCsvWaveLines - 1 ? lane + 1 : lane);
+   const bool tail = key >= 0 && (lane == kCsvWaveLines - 1 || next != key);
+   if (tail && bits > 0 && b0 + key < a.nbins) atomicMax(a.bins + (b0 + key), bits); }
 
 }  // namespace rtfe

@@ -264,6 +264,9 @@ def _load_library(path=None):
         lib.rtfe_csv_peak.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_float, C.c_void_p, C.c_void_p]
         lib.rtfe_csv_parse.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_float, C.c_float,
                                        C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(lib, "rtfe_csv_graph"):                     # the converter's -graph / -redo peak (csvin.read_csv_device, convert_csv_device)
+        lib.rtfe_csv_graph.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_float, C.c_int64, C.c_int64, C.c_void_p, C.c_int64,
+                                       C.c_void_p, C.c_void_p]
     if hasattr(lib, "rtfe_csv_format"):                    # rows -> CSV text on the device (csvout.write_csv_device)
         lib.rtfe_csv_format_max_bytes.argtypes = [C.c_int64, C.c_int]; lib.rtfe_csv_format_max_bytes.restype = C.c_size_t
         lib.rtfe_csv_format_scratch_bytes.argtypes = [C.c_int64]; lib.rtfe_csv_format_scratch_bytes.restype = C.c_size_t
