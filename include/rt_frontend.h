@@ -200,6 +200,26 @@ int rtfe_pack_events(rtfe_handle *h, const rtfe_burst *d_bursts, const int32_t *
  * passing over the window on the host. */
 int rtfe_find_end_mark(rtfe_handle *h, const int16_t *d_rows, int64_t nrows, int64_t *d_first, void *stream);
 
+/* -subsample on a raw window (src/readtape.c:1407-1424: of every n rows the reader uses the last one, but looks for the end marker on all of them).
+ * Handle-free and queued on `stream`: no host synchronisation, no allocation.  The ABI version did not move: an addition, and rtfe_kernel_count() stays
+ * what it was (this kernel is no span of a scan).
+ *   d_out row j = d_in row first + j * step, for every j with first + j * step < nrows_in (rows of ntrks int16; step 1 is a plain copy);
+ *   *d_first_mark = rtfe_find_end_mark's answer over the RAW rows: the smallest row of d_in[0 .. nrows_in) whose head-0 sample is 0x8000, INT64_MAX if there
+ *   is none - the skipped rows and the rows in front of `first` included, and also when there is no row to write.
+ * The kernel does not clip at the marker: the caller keeps row j iff first + j * step < *d_first_mark (a group of `step` rows that the marker cuts short is
+ * dropped, as the reader drops it).  A streaming reader calls it with first = step - 1 between a window's upload and its rtfe_scan, in place of
+ * rtfe_find_end_mark.
+ * Memory contract: reads exactly the bytes of d_in[0 .. nrows_in) - none behind the last source row, the window's last, partial 16-byte vector is fetched
+ * sample by sample - and writes exactly the bytes of the rows listed above and the 8 bytes of *d_first_mark: none in front of d_out, none behind its last
+ * written row (that row's partial 16-byte vector is stored sample by sample).
+ * Refusals, all before anything is queued (d_out and *d_first_mark are left alone): a null pointer: -1; ntrks outside 1 .. 19: -3; step < 1, first < 0,
+ * nrows_in < 0 or more rows than a launch takes: -34; d_in or d_out not 16-byte aligned: -31; out_cap_rows smaller than the rows to write: -32; the byte
+ * ranges of d_in[0 .. nrows_in) and of the rows to write overlap (in place is not supported): -37.  rtfe_last_error says which.
+ * rtfe_decimate_span_rows(ntrks): the raw rows one workgroup (one wave) of the kernel takes - a multiple of 8; for tests and tools that aim at its seams. */
+int64_t rtfe_decimate_span_rows(int ntrks);
+int rtfe_decimate_rows(const int16_t *d_in, int64_t nrows_in, int ntrks, int64_t first, int64_t step, int16_t *d_out, int64_t out_cap_rows,
+                       int64_t *d_first_mark, void *stream);
+
 /* Per-kernel timing: with enable != 0, rtfe_scan records HIP events on `stream` around each of its timed spans (rtfe_kernel_name), one
  * set of events per scan in a ring of 64 sets - nothing waits, so scans queued back to back stay back to back.  rtfe_kernel_ms synchronises
  * the sets recorded since its last call and returns, per span, the elapsed milliseconds SUMMED over those scans (out[rtfe_kernel_count()]);

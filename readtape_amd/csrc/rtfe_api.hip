@@ -984,6 +984,29 @@ extern "C" int rtfe_find_end_mark(rtfe_handle *h, const int16_t *d_rows, int64_t
    if (e != hipSuccess) return fail(-30, "rtfe_find_end_mark: %s", hipGetErrorString(e));
    return 0; }
 
+extern "C" int64_t rtfe_decimate_span_rows(int ntrks) { return ntrks >= 1 && ntrks <= RTFE_MAXTRKS ? dec_span_rows(ntrks) : 0; }
+
+extern "C" int rtfe_decimate_rows(const int16_t *d_in, int64_t nrows_in, int ntrks, int64_t first, int64_t step, int16_t *d_out, int64_t out_cap_rows,
+                                  int64_t *d_first_mark, void *stream) {
+   if (!d_in || !d_out || !d_first_mark) return fail(-1, "rtfe_decimate_rows: null argument");
+   if (ntrks < 1 || ntrks > RTFE_MAXTRKS) return fail(-3, "rtfe_decimate_rows: ntrks %d out of range", ntrks);
+   if (step < 1 || first < 0 || nrows_in < 0) return fail(-34, "rtfe_decimate_rows: bad row range (nrows_in %lld, first %lld, step %lld)", (long long)nrows_in, (long long)first, (long long)step);
+   if ((((uintptr_t)d_in | (uintptr_t)d_out) & 15) != 0) return fail(-31, "rtfe_decimate_rows: d_in and d_out must be 16-byte aligned");
+   const int span = dec_span_rows(ntrks);
+   const long long nwg = (nrows_in + span - 1) / span;
+   if (nwg > 0x7fffffffll) return fail(-34, "rtfe_decimate_rows: %lld rows are more than a launch takes", (long long)nrows_in);
+   if (step > nrows_in) step = nrows_in > 0 ? nrows_in : 1;          // (the same rows: out row 0 only, if any - and no sum below leaves 64 bits)
+   const long long nkept = first < nrows_in ? (nrows_in - first + step - 1) / step : 0;
+   if (out_cap_rows < nkept) return fail(-32, "rtfe_decimate_rows: %lld rows to write, room for %lld", nkept, (long long)out_cap_rows);
+   const uintptr_t rb = 2 * (uintptr_t)ntrks, i0 = (uintptr_t)d_in, i1 = i0 + (uintptr_t)nrows_in * rb, o0 = (uintptr_t)d_out, o1 = o0 + (uintptr_t)nkept * rb;
+   if (i0 < o1 && o0 < i1) return fail(-37, "rtfe_decimate_rows: d_in and d_out overlap (in place is not supported)");
+   hipStream_t st = (hipStream_t)stream;
+   hipLaunchKernelGGL(k_end_mark_init, dim3(1), dim3(1), 0, st, reinterpret_cast<long long *>(d_first_mark));
+   if (nwg > 0)
+      hipLaunchKernelGGL(k_decimate, dim3((unsigned)nwg), dim3(kDecWave), 0, st, d_in, (long long)nrows_in, ntrks, (long long)first, (long long)step, span, d_out,
+                         reinterpret_cast<long long *>(d_first_mark));
+   return launch_check("rtfe_decimate_rows"); }
+
 extern "C" int rtfe_reset_floor(rtfe_handle *h, void *stream) {
    if (!h) return fail(-1, "null argument");
    hipLaunchKernelGGL(k_reset_floor, dim3(1), dim3(1), 0, (hipStream_t)stream, h->d_dev);

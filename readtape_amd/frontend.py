@@ -272,9 +272,26 @@ def _load_library(path=None):
         lib.rtfe_csv_format_scratch_bytes.argtypes = [C.c_int64]; lib.rtfe_csv_format_scratch_bytes.restype = C.c_size_t
         lib.rtfe_csv_format_path.argtypes = [C.c_int64, C.c_int64, C.c_void_p]
         lib.rtfe_csv_format.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+    if hasattr(lib, "rtfe_decimate_rows"):                 # -subsample on a raw window (decimate_rows; ingest.decode_file_streaming)
+        lib.rtfe_decimate_span_rows.argtypes = [C.c_int]; lib.rtfe_decimate_span_rows.restype = C.c_int64
+        lib.rtfe_decimate_rows.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     if lib.rtfe_abi_version() != 6:
         raise RuntimeError("librtfe.so ABI mismatch")
     return lib
+
+
+def decimate_rows(lib, backend, d_in, nrows_in, first, step, d_out, d_first_mark, stream=None):
+    """rtfe_decimate_rows: d_out[j] = d_in[first + j * step] for the first `nrows_in` rows of d_in, and the first raw row whose head-0 sample is the end
+    marker into d_first_mark (8 bytes, INT64_MAX if none) - queued on `stream` (default: the backend's current one), nothing waits.  d_in, d_out: [rows, ntrks]
+    int16, device tensors or the emulator backend's arrays; d_first_mark: a buffer of the backend's.  Returns the rows written (the caller clips at the marker)."""
+    ntrks = int(d_in.shape[1])
+    if d_in.ndim != 2 or d_out.ndim != 2 or int(d_out.shape[1]) != ntrks or int(d_in.shape[0]) < nrows_in:
+        raise ValueError(f"decimate_rows: d_in {tuple(d_in.shape)}, d_out {tuple(d_out.shape)}, nrows_in {nrows_in}")
+    rc = lib.rtfe_decimate_rows(backend.ptr(d_in), int(nrows_in), ntrks, int(first), int(step), backend.ptr(d_out), int(d_out.shape[0]), backend.ptr(d_first_mark),
+                                stream if stream is not None else backend.stream())
+    if rc != 0:
+        raise RuntimeError(f"rtfe_decimate_rows failed ({rc}): {lib.rtfe_last_error().decode()}")
+    return len(range(int(first), int(nrows_in), int(step)))
 
 
 class ScanResult:
@@ -499,9 +516,12 @@ class FrontEnd:
             raise ValueError(f"rows must be [n, {self.cfg.ntrks}] int16, got {tuple(d_rows.shape)}")
         return d_rows
 
-    def scan(self, rows, row_base=0, first_is_tape_start=True, stream=None, own_rows=None) -> ScanResult:
+    def scan(self, rows, row_base=0, first_is_tape_start=True, stream=None, own_rows=None, raw=None) -> ScanResult:
         """Launches the speculative scan of `rows` ([n, ntrks] int16, device tensor or numpy) — asynchronous.
-        Time shards pass own_rows < n: the trailing rows are the right neighbour's halo (include/rt_frontend.h)."""
+        Time shards pass own_rows < n: the trailing rows are the right neighbour's halo (include/rt_frontend.h).
+        raw = (d_raw, first, step, thinned) (the streaming reader with -subsample; needs pack_on_scan): `rows` is not filled yet - in front of the scan, on
+        its stream, rtfe_decimate_rows writes rows[j] = d_raw[first + j * step] for all len(rows) * step rows of d_raw, and its end mark (a RAW row of d_raw)
+        comes back as the result's end_mark, where rtfe_find_end_mark's would.  thinned (may be None) is called when that is queued: d_raw is free behind it."""
         be = self.backend
         d_rows = self._rows(rows)
         nrows = int(d_rows.shape[0])
@@ -512,7 +532,15 @@ class FrontEnd:
         marked = False
         import time
         lt = [time.perf_counter()]
-        if getattr(self, "find_end_mark", False) and pack_now:      # (the streaming reader: the window's end-of-data check on the device, in front of the scan)
+        if raw is not None:                                # (the streaming reader with -subsample: the window is thinned where it was uploaded; the check comes with it)
+            if not pack_now:
+                raise RuntimeError("scan(raw=...) needs pack_on_scan (the end mark comes back with the packed tables)")
+            d_raw, first, step, thinned = raw
+            decimate_rows(self.lib, be, d_raw, nrows * int(step), first, step, d_rows, b["endmark"], stream)
+            marked = True
+            if thinned is not None:
+                thinned()
+        elif getattr(self, "find_end_mark", False) and pack_now:      # (the streaming reader: the window's end-of-data check on the device, in front of the scan)
             if self.lib.rtfe_find_end_mark(self.h, be.ptr(d_rows), nrows, be.ptr(b["endmark"]), stream if stream is not None else be.stream()) != 0:
                 raise RuntimeError(f"rtfe_find_end_mark failed: {self.lib.rtfe_last_error().decode()}")
             marked = True

@@ -8,7 +8,8 @@ Replaces the reference's read loop (two fread()s per row into a stack buffer, sr
 A software pipeline of threads (the interpreter lock is the scarce resource: whatever runs per row or per event runs in native code):
   - the producer reads window after window into a ring of pinned buffers (rt_read_mt: native threads, positional reads) and queues each
     window's upload (copy stream) and, behind it on the scan stream, rtfe_find_end_mark (the reader's end-of-data check, on the device),
-    rtfe_scan, rtfe_pack_events and the copies of the small tables into page-locked memory - `scan_contexts` windows are in flight;
+    rtfe_scan, rtfe_pack_events and the copies of the small tables into page-locked memory - `scan_contexts` windows are in flight (with
+    subsample > 1 the upload goes to a raw staging buffer and rtfe_decimate_rows - thinning and end-of-data check in one - fills the window);
   - a fetcher per context waits for its window's event, copies the packed event lists to the host and hands the window to the replay pool;
   - a replay task per window runs its sub-fragments on native threads (rt_replay_run_fragments) and collects their pieces of the .tap;
   - the caller's thread concatenates the pieces in window order.
@@ -46,32 +47,77 @@ class _All:
             f.result()
 
 
-def decode_file_streaming(path, tap_path, window_rows=1 << 24, halo_rows=1 << 17, opts: pipeline.DecodeOptions | None = None, cfgkw=None,
-                          device="cuda:0", replay_threads: int = 1, read_threads: int = 4, replay_split: int = 1, scan_contexts: int = 3, ramp: bool = True):
-    """Decodes the .tbin file `path` to the SIMH file `tap_path` through device windows of `window_rows` rows (a multiple of 1024).
-    Returns statistics incl. the end-to-end rate (disk -> .tap), the time spent in the host replay and the rows the halos re-read.
-    replay_threads > 1: the windows' host replays run side by side (fragments are independent: each has its own decoder context
-    and writes its own piece of the .tap; the pieces are concatenated in window order).  A window's device buffer is kept until
-    its replay is done (exact rescans read it), so replay_threads + 2 device windows are held.
-    replay_split > 1: a window's bursts are replayed as that many sub-fragments side by side (cut at burst boundaries, exactly as the
-    windows themselves are); the last two windows - what the pipeline drains into - as four times as many.
-    scan_contexts: scans in flight (a context = a front end with its workspace and output buffers; a context is free again once its window's
-    results have been fetched).  ramp: the first two windows are a quarter and a half of `window_rows` (the pipeline fills sooner)."""
-    import queue
+def _prepasses(hdr, fd, off, nrows, nth, full, opts, cfgkw, deskew, prepass_rows, device):
+    """What the reference settles before its main pass (src/readtape.c:1656-1717), on a prefix of the file: the density of a header without one, then the
+    -deskew delays with that density - pipeline.detect_density / calibrate_deskew, which the resident decode runs on its whole tape.  -> cfgkw with what they
+    found ("bpi", "skew"); unchanged, and nothing read or launched, where neither is asked for.  off: the payload behind the skipped rows; nrows: used rows."""
+    need_bpi = hdr.mode != tbin.MODE_GCR and not hdr.bpi > 0 and not cfgkw.get("bpi")
+    need_skew = bool(deskew) and cfgkw.get("skew") is None and hdr.mode != tbin.MODE_PE      # "-deskew option is ignored for PE", src/readtape.c:1677
+    if not (need_bpi or need_skew) or nrows <= 0:
+        return cfgkw
+    if need_bpi and hdr.mode != tbin.MODE_NRZI:
+        pipeline.detect_density(hdr, None, full, None, None)      # (raises what the resident decode raises: density detection is NRZI's)
     import torch
-    assert window_rows % 1024 == 0
-    t_enter = time.perf_counter()
-    opts = opts or pipeline.DecodeOptions()
-    hdr, off, nrows = _payload_geometry(path)
-    if hdr.mode == tbin.MODE_WW:
-        raise NotImplementedError("Whirlwind tapes are one chain (no independent fragments): read the file and use pipeline.decode_tape_ww")
     ntrks = hdr.ntrks
-    full = pipeline.default_parmsets(hdr.mode, opts.nparmsets or (15 if opts.multiple_tries else 1))
-    cfg = frontend.FrontEndConfig.from_header(hdr, parmsets=pipeline.frontend_parmsets(full), **(cfgkw or {}))
-    nctx = max(2, int(scan_contexts))
-    fes = [frontend.FrontEnd(cfg, device=device) for _ in range(nctx)]      # window k is fetched while k + 1 .. are copied and scanned
-    fe = fes[0]
     dev = torch.device(device)
+    be, lib, dlib = frontend.TorchBackend(device), frontend._load_library(), pipeline._load_decode_lib()
+    make_fe = lambda c: frontend.FrontEnd(c, device=device)
+    invert, find_zeros, differentiate = (bool(cfgkw.get(k, False)) for k in ("invert", "find_zeros", "differentiate"))
+
+    def options(bpi):
+        return pipeline._Options(mode=hdr.mode, ntrks=ntrks, bpi=bpi, ips=hdr.ips or 50.0, specified_parity=0 if opts.even_parity else 1, revparity=opts.revparity,
+                                 do_correction=int(opts.correct), find_zeros=int(find_zeros), do_differentiate=int(differentiate),
+                                 multiple_tries=int(opts.multiple_tries), tap_format=1, add_parity=0, verbose=int(opts.verbose))
+
+    def prefix(want):
+        """the used rows [0, want) on the device, cut at the end marker -> (rows, whether the tape goes on behind them)"""
+        host = torch.empty((want * nth, ntrks), dtype=torch.int16, pin_memory=True)
+        if dlib.rt_read_mt(fd, host.numpy().ctypes.data, off, want * nth * 2 * ntrks, 4) != 0:
+            raise IOError("short read")
+        d_raw = host.to(dev, non_blocking=True)
+        rows, d_mark = torch.empty((want, ntrks), dtype=torch.int16, device=dev), be.empty(16)
+        frontend.decimate_rows(lib, be, d_raw, want * nth, nth - 1, nth, rows, d_mark)      # (step 1: a copy and the end-of-data check)
+        m = int(be.to_numpy(d_mark, np.int64)[0])
+        used = want if m == np.iinfo(np.int64).max else min(want, m // nth)
+        return rows[:used], used == want and want < nrows
+
+    def run(what, fn):
+        want = min(nrows, max(1024, prepass_rows))
+        while True:
+            try:
+                rows, more = prefix(want)
+                got = fn(rows, more)
+            except torch.cuda.OutOfMemoryError as e:
+                raise RuntimeError(f"{what}: undecided on the longest prefix the device holds (a prefix of {want} rows does not fit): nothing was decoded") from e
+            if got is not None:
+                return got
+            del rows
+            want = min(nrows, want * 4)                    # (None only with more rows behind the prefix: want < nrows)
+
+    cfgkw = dict(cfgkw)
+    if need_bpi:
+        cfgkw["bpi"] = run("density detection", lambda rows, more: pipeline.detect_density(
+            hdr, rows, full, options(0.0), make_fe, invert=invert, first_prefix_rows=max(1, int(rows.shape[0])), more_rows=more))
+    if need_skew:
+        rest = {k: v for k, v in cfgkw.items() if k not in ("invert", "find_zeros", "differentiate", "skew")}
+        bpi = frontend.FrontEndConfig.from_header(hdr, **({"bpi": cfgkw["bpi"]} if "bpi" in cfgkw else {})).bpi
+        cfgkw["skew"] = run("-deskew calibration", lambda rows, more: pipeline.calibrate_deskew(
+            hdr, rows, full, options(bpi), make_fe, invert=invert, find_zeros=find_zeros, differentiate=differentiate,
+            first_prefix_rows=max(1, int(rows.shape[0])), more_rows=more, **rest))
+    return cfgkw
+
+
+def plan_windows(raw_rows, window_rows, halo_rows, subsample=1, skip=0, ramp=True):
+    """The windows of a payload of `raw_rows` rows -> [(lo, hi, raw_lo, raw_hi), ...].
+    Windows are planned in USED rows - the rows the scans see: of every `subsample` raw rows behind the first `skip`, the last (src/readtape.c:1407-1424,
+    1634-1641) - so that the cuts stay on the 1024-row grid the fragments' ownership rule stands on.  Window k owns the used rows [lo, hi)
+    and is scanned with a halo of up to halo_rows further ones; the raw rows it is made of are [raw_lo, raw_hi) = [skip + lo * n, skip + min(hi + halo_rows,
+    used rows) * n).  An incomplete group of raw rows at the end of the payload is no used row.
+    ramp: the first two windows are a quarter and a half of window_rows (the pipeline fills sooner), and the last two windows' worth of rows go as a
+    half, a quarter and two eighths of what is left (it drains sooner) - for windows of 2^20 rows and more."""
+    assert window_rows % 1024 == 0 and window_rows > 0 and halo_rows >= 0 and subsample >= 1 and skip >= 0
+    n = int(subsample)
+    nrows = max(0, int(raw_rows) - int(skip)) // n
     spans, lo = [], 0
     sizes = [window_rows // 4 & ~1023, window_rows // 2 & ~1023] if (ramp and window_rows >= (1 << 20) and nrows > 2 * window_rows) else []
     while lo < nrows:
@@ -88,13 +134,81 @@ def decode_file_streaming(path, tap_path, window_rows=1 << 24, halo_rows=1 << 17
             break
         spans.append((lo, min(nrows, lo + w)))
         lo += w
+    return [(lo, hi, skip + lo * n, skip + min(nrows, hi + halo_rows) * n) for lo, hi in spans]
+
+
+def decode_file_streaming(path, tap_path, window_rows=1 << 24, halo_rows=1 << 17, opts: pipeline.DecodeOptions | None = None, cfgkw=None,
+                          device="cuda:0", replay_threads: int = 1, read_threads: int = 4, replay_split: int = 1, scan_contexts: int = 3, ramp: bool = True,
+                          subsample: int = 1, skip: int = 0, deskew: bool = False, skew=None, prepass_rows: int = 1 << 22):
+    """Decodes the .tbin file `path` to the SIMH file `tap_path` through device windows of `window_rows` rows (a multiple of 1024).
+    Returns statistics incl. the end-to-end rate (disk -> .tap), the time spent in the host replay and the rows the halos re-read.
+    replay_threads > 1: the windows' host replays run side by side (fragments are independent: each has its own decoder context
+    and writes its own piece of the .tap; the pieces are concatenated in window order).  A window's device buffer is kept until
+    its replay is done (exact rescans read it), so replay_threads + 2 device windows are held.
+    replay_split > 1: a window's bursts are replayed as that many sub-fragments side by side (cut at burst boundaries, exactly as the
+    windows themselves are); the last two windows - what the pipeline drains into - as four times as many.
+    scan_contexts: scans in flight (a context = a front end with its workspace and output buffers; a context is free again once its window's
+    results have been fetched).  ramp: the first two windows are a quarter and a half of `window_rows` (the pipeline fills sooner).
+    The reference's reader options (statistics: rows = the USED rows decoded, raw_rows = the payload rows they stand for, the skipped ones included):
+      skip       the first `skip` rows of the payload are not part of the tape: the time base does not advance over them and an end marker among them is not
+                 looked at (src/readtape.c:1634-1641) - the decode of rows[skip:].
+      subsample  n: of every n raw rows behind the skip the last one is used, the time base advances by the header's tdelta per used row, and the data end at
+                 the first RAW row whose head-0 sample is 0x8000, used or not (src/readtape.c:1407-1424) - the decode of rows[skip:][n - 1::n].  Windows,
+                 halos and window_rows count used rows (plan_windows); each window is uploaded raw and thinned on the device (rtfe_decimate_rows, which
+                 also is its end-of-data check).  Memory: the pinned buffers and scan_contexts + 1 raw device staging buffers hold n times a window's
+                 rows; the device windows themselves do not grow.
+      density    a header without bpi (NRZI): pipeline.detect_density on a prefix of the used rows; PE raises what the resident decode raises.
+      deskew     pipeline.calibrate_deskew on a prefix, with the detected density, unless `skew` (the delays, in samples per track) is given or the mode is PE.
+    The pre-passes run before the pipeline starts, on the first prepass_rows used rows read the reader's way (pinned, uploaded, thinned), with the main pass's
+    invert / find_zeros / differentiate and no delays.  A pre-pass whose stopping rule is not met inside the prefix gets a prefix four times as long, up
+    to the whole tape; if that does not fit the device a RuntimeError says so (nothing is ever streamed with a guessed density or partial delays).
+    statistics["bpi"], ["skew"]: what the scans ran with.  With the defaults and a header that states its density nothing of this costs a launch or a buffer."""
+    import queue
+    import torch
+    assert window_rows % 1024 == 0
+    t_enter = time.perf_counter()
+    opts = opts or pipeline.DecodeOptions()
+    hdr, off, raw_rows = _payload_geometry(path)
+    if hdr.mode == tbin.MODE_WW:
+        raise NotImplementedError("Whirlwind tapes are one chain (no independent fragments): read the file and use pipeline.decode_tape_ww")
+    nth, skip = int(subsample), int(skip)
+    if nth < 1 or skip < 0:
+        raise ValueError(f"subsample {subsample} (at least 1), skip {skip} (not negative)")
+    ntrks = hdr.ntrks
+    plan = plan_windows(raw_rows, window_rows, halo_rows, nth, skip, ramp)
+    spans = [(lo, hi) for lo, hi, _, _ in plan]
+    off += skip * 2 * ntrks                               # (the payload, from here on: what lies behind the skipped rows)
+    nrows = max(0, raw_rows - skip) // nth               # used rows: every row index below counts these
+    gpu_mark = os.environ.get("RTFE_PACK_EVENTS") != "0" and not os.environ.get("RT_INGEST_HOST_MARK")
+    if nth > 1 and not gpu_mark:
+        raise NotImplementedError("subsample > 1: the windows' end-of-data check is the thinning kernel's (unset RT_INGEST_HOST_MARK / RTFE_PACK_EVENTS=0)")
+    full = pipeline.default_parmsets(hdr.mode, opts.nparmsets or (15 if opts.multiple_tries else 1))
+    dev = torch.device(device)
+    cfgkw = dict(cfgkw or {})
+    if skew is not None:
+        cfgkw["skew"] = [int(x) for x in skew]
+    fd = os.open(path, os.O_RDONLY)
+    try:
+        cfgkw = _prepasses(hdr, fd, off, nrows, nth, full, opts, cfgkw, deskew, int(prepass_rows), device)
+    except BaseException:
+        os.close(fd)
+        raise
+    cfg = frontend.FrontEndConfig.from_header(hdr, parmsets=pipeline.frontend_parmsets(full), **cfgkw)
+    nctx = max(2, int(scan_contexts))
+    fes = [frontend.FrontEnd(cfg, device=device) for _ in range(nctx)]      # window k is fetched while k + 1 .. are copied and scanned
+    fe = fes[0]
     cap = window_rows + halo_rows
     from concurrent.futures import ThreadPoolExecutor
     nthreads = max(1, int(replay_threads))
     depth = max(2 if nthreads == 1 else nthreads + 2, nctx + 2)
     NP = nctx + 1                                         # pinned buffers: one being read into, the others being copied from / waiting for their context
-    pinned = [torch.empty((cap, ntrks), dtype=torch.int16, pin_memory=True) for _ in range(NP)]      # hipHostMalloc
+    pinned = [torch.empty((cap * nth, ntrks), dtype=torch.int16, pin_memory=True) for _ in range(NP)]      # hipHostMalloc
     dwin = [torch.empty((cap, ntrks), dtype=torch.int16, device=dev) for _ in range(depth)]
+    # -subsample: a window is uploaded raw into a staging buffer and thinned from there into its device window, on the scan's stream in front of the scan; the
+    # staging buffer is free again when that has run (`thinned`), so there are as many as pinned buffers - the device windows, which the replays' exact
+    # rescans keep reading, stay as they are
+    staging = [torch.empty((cap * nth, ntrks), dtype=torch.int16, device=dev) for _ in range(NP)] if nth > 1 else None
+    thinned = [torch.cuda.Event() for _ in range(NP)] if nth > 1 else None
     pool = ThreadPoolExecutor(max(2, -(-nthreads // max(1, int(replay_split))))) if nthreads > 1 else None      # a task is a window: its sub-fragments are native threads
     read_threads = max(1, int(read_threads))
     readers = ThreadPoolExecutor(read_threads) if read_threads > 1 else None
@@ -102,7 +216,6 @@ def decode_file_streaming(path, tap_path, window_rows=1 << 24, halo_rows=1 << 17
     exact_lock = threading.Lock()
     copy_stream, scan_stream = torch.cuda.Stream(dev), torch.cuda.Stream(dev)
     copied = [torch.cuda.Event() for _ in range(NP)]
-    fd = os.open(path, os.O_RDONLY)
     dlib = pipeline._load_decode_lib()
     t_read = [0.0]
     trace = [] if os.environ.get("RT_INGEST_TRACE") else None      # (stage, window, start, end) in seconds since the timed region began
@@ -114,16 +227,15 @@ def decode_file_streaming(path, tap_path, window_rows=1 << 24, halo_rows=1 << 17
     data_end = [nrows]
     end_lock = threading.Lock()
 
-    gpu_mark = hasattr(fe.backend, "pinned") and os.environ.get("RTFE_PACK_EVENTS") != "0" and not os.environ.get("RT_INGEST_HOST_MARK")
-    for f in fes:                                          # the end-of-data marker is looked for on the device, in front of each window's scan (rtfe_find_end_mark)
+    for f in fes:                                         # the end-of-data marker is looked for on the device, in front of each window's scan (rtfe_find_end_mark)
         f.pack_on_scan, f.find_end_mark = True, gpu_mark
 
     def read_span(arr, r0, r1, lo, check=True):
-        """rows [lo + r0, lo + r1) of the payload -> arr[r0:r1]; returns the first row (relative to lo) whose head-0 sample is the end
-        marker, or -1 (looked for here, by the thread that has just read the rows: a strided pass over the whole window in one
+        """raw rows [lo * nth + r0, lo * nth + r1) of the payload -> arr[r0:r1]; returns the first of them (relative to lo * nth) whose head-0
+        sample is the end marker, or -1 (looked for here, by the thread that has just read the rows: a strided pass over the whole window in one
         thread had become the longest stage of the pipeline)."""
         view = memoryview(arr).cast("B")[r0 * 2 * ntrks: r1 * 2 * ntrks]
-        pos, done = off + (lo + r0) * 2 * ntrks, 0
+        pos, done = off + (lo * nth + r0) * 2 * ntrks, 0
         while done < len(view):
             got = os.preadv(fd, [view[done: done + (1 << 30)]], pos + done)
             if got <= 0:
@@ -135,13 +247,14 @@ def decode_file_streaming(path, tap_path, window_rows=1 << 24, halo_rows=1 << 17
         return r0 + int(marks[0]) if marks.size else -1
 
     def read_rows(dst, lo, end, check=True):
-        """rows [lo, end) of the payload -> the pinned tensor dst (positional reads: safe beside the other thread's), in `read_threads`
-        pieces side by side (from the page cache one thread copies ~13 GB/s).  Returns the first end-marker row (relative to lo) or -1."""
+        """the raw rows of the used rows [lo, end) of the payload -> the pinned tensor dst (positional reads: safe beside the other thread's), in
+        `read_threads` pieces side by side (from the page cache one thread copies ~13 GB/s).  Returns the used rows (behind lo) in front of the first
+        end marker, or -1."""
         t0 = time.perf_counter()
         arr = dst.numpy()
-        n = end - lo
+        n = (end - lo) * nth
         if not check:                                      # (the end marker is looked for on the device: the read is one call into native threads)
-            if dlib.rt_read_mt(fd, arr.ctypes.data, off + lo * 2 * ntrks, n * 2 * ntrks, read_threads) != 0:
+            if dlib.rt_read_mt(fd, arr.ctypes.data, off + lo * nth * 2 * ntrks, n * 2 * ntrks, read_threads) != 0:
                 raise IOError("short read")
             first = -1
         elif readers is None or n * 2 * ntrks < (8 << 20):
@@ -152,7 +265,7 @@ def decode_file_streaming(path, tap_path, window_rows=1 << 24, halo_rows=1 << 17
             hits = [h for h in (f.result() for f in futs) if h >= 0]
             first = min(hits) if hits else -1
         t_read[0] += time.perf_counter() - t0
-        return first
+        return first // nth if first >= 0 else -1         # (a group of nth rows that the marker cuts short is no used row)
 
     def read_window(k):
         lo, hi = spans[k]
@@ -184,14 +297,20 @@ def decode_file_streaming(path, tap_path, window_rows=1 << 24, halo_rows=1 << 17
         with torch.cuda.stream(copy_stream):
             if trace is not None:
                 gpu_ev[("copy0", k)] = torch.cuda.Event(enable_timing=True); gpu_ev[("copy0", k)].record(copy_stream)
-            dwin[k % depth][: end - lo].copy_(pinned[k % NP][: end - lo], non_blocking=True)
+            if nth == 1:
+                dwin[k % depth][: end - lo].copy_(pinned[k % NP][: end - lo], non_blocking=True)
+            else:
+                if k >= NP:
+                    copy_stream.wait_event(thinned[k % NP])      # window k - NP has been thinned out of this staging buffer
+                staging[k % NP][: (end - lo) * nth].copy_(pinned[k % NP][: (end - lo) * nth], non_blocking=True)
             copied[k % NP].record(copy_stream)
             if trace is not None:
                 gpu_ev[("copy1", k)] = torch.cuda.Event(enable_timing=True); gpu_ev[("copy1", k)].record(copy_stream)
         mark("l_h2d", k, t0)
         scan_stream.wait_event(copied[k % NP])
         piece = dwin[k % depth][: end - lo]
-        fin = pipeline.scan_fragment(fes[k % nctx], piece, hi - lo, lo, lo == 0, hi >= data_end[0], stream=scan_stream.cuda_stream)
+        raw = (staging[k % NP][: (end - lo) * nth], nth - 1, nth, lambda: thinned[k % NP].record(scan_stream)) if nth > 1 else None
+        fin = pipeline.scan_fragment(fes[k % nctx], piece, hi - lo, lo, lo == 0, hi >= data_end[0], stream=scan_stream.cuda_stream, raw=raw)
         if trace is not None:
             gpu_ev[("scan1", k)] = torch.cuda.Event(enable_timing=True); gpu_ev[("scan1", k)].record(scan_stream)
         mark("launch", k, t0)
@@ -298,9 +417,10 @@ def decode_file_streaming(path, tap_path, window_rows=1 << 24, halo_rows=1 << 17
                     assert res.end_mark_valid
                     if lo >= data_end[0]:
                         return []
-                    if res.end_mark is not None and res.end_mark < end_k - lo:
+                    em = None if res.end_mark is None else res.end_mark // nth      # (the thinning kernel reports a RAW row of the window: the used rows in front of it)
+                    if em is not None and em < end_k - lo:
                         with end_lock:
-                            data_end[0] = min(data_end[0], lo + res.end_mark)
+                            data_end[0] = min(data_end[0], lo + em)
                         end_k = min(end_k, data_end[0])
                         hi = min(hi, data_end[0])
                         if hi <= lo:
@@ -340,13 +460,17 @@ def decode_file_streaming(path, tap_path, window_rows=1 << 24, halo_rows=1 << 17
                 halo *= 4
                 stats["retries"] += 1
                 end_k = min(data_end[0], hi + halo)
-                host = torch.empty((end_k - lo, ntrks), dtype=torch.int16, pin_memory=True)
+                host = torch.empty(((end_k - lo) * nth, ntrks), dtype=torch.int16, pin_memory=True)
                 first = read_rows(host, lo, end_k)
                 if first >= 0:                            # an end marker inside the longer halo: the tape ends there (src/readtape.c:1410)
                     with end_lock:
                         data_end[0] = min(data_end[0], lo + first)
                     end_k = min(end_k, data_end[0])
-                piece = host[: end_k - lo].to(dev)
+                piece = host[: (end_k - lo) * nth].to(dev)
+                if nth > 1:                              # (-subsample: the longer window is thinned as the windows are; its marker has been looked for above)
+                    wide, piece = piece, torch.empty((end_k - lo, ntrks), dtype=torch.int16, device=dev)
+                    frontend.decimate_rows(fe.lib, fe.backend, wide, (end_k - lo) * nth, nth - 1, nth, piece, fe.backend.empty(16))
+                    torch.cuda.current_stream(dev).synchronize()      # (`wide` goes out of scope: the allocator may hand it to another stream)
                 res, nb, bound = pipeline.scan_fragment(res.fe, piece, hi - lo, lo, lo == 0, hi >= data_end[0])()
             stats["halo_rows_read"] += end_k - hi
             if res.nbursts:
@@ -426,5 +550,6 @@ def decode_file_streaming(path, tap_path, window_rows=1 << 24, halo_rows=1 << 17
                 trace.append(("gpu_copy", k, c0 / 1e3, c1 / 1e3)); trace.append(("gpu_scan_done", k, c1 / 1e3, s1 / 1e3))
         stats["trace"] = sorted(trace, key=lambda x: x[2])
     stats.update(setup_seconds=t_start - t_enter, rows=data_end[0], seconds=dt, msamples_per_s=data_end[0] / dt / 1e6, replay_seconds=t_replay, read_seconds=t_read[0], scan_wait_seconds=wait_s[0],
-                 replay_events_per_s=(stats["events_delivered"] / t_replay) if t_replay > 0 else None, tap_bytes=total + (4 if total else 0), screen_floor_height=floor_state["floor"])
+                 replay_events_per_s=(stats["events_delivered"] / t_replay) if t_replay > 0 else None, tap_bytes=total + (4 if total else 0), screen_floor_height=floor_state["floor"],
+                 raw_rows=skip + data_end[0] * nth, bpi=cfg.bpi, skew=list(cfg.skew) if cfg.skew is not None else None)
     return stats

@@ -158,11 +158,13 @@ def _release(keep):
 
 
 def calibrate_deskew(hdr, rows, full, o, fe_factory, invert=False, find_zeros=False, differentiate=False,
-                     log_path=None, evt_path=None, first_prefix_rows=1 << 22, append=False, **cfgkw):
+                     log_path=None, evt_path=None, first_prefix_rows=1 << 22, append=False, more_rows=False, **cfgkw):
     """The -deskew pre-pass (src/readtape.c:1675-1717) on the device front end: scans a prefix of the resident tape with
     NO deskew delays and the first parameter set, lets the host decoders record where each track's transitions fall,
     and returns the per-track delays in samples.  The prefix grows until the reference's stopping rule (1000
-    transitions on every track, or 100 blocks) is met inside it, or it is the whole tape."""
+    transitions on every track, or 100 blocks) is met inside it, or it is the whole tape.
+    more_rows: `rows` is itself a prefix of a longer tape (the streaming reader's): where the rule is not met inside all of
+    `rows` the answer is None - undecided, come back with more - instead of what the rows at hand would give."""
     lib = _load_decode_lib()
     nrows = int(rows.shape[0])
     n0 = min(nrows, first_prefix_rows)
@@ -191,17 +193,20 @@ def calibrate_deskew(hdr, rows, full, o, fe_factory, invert=False, find_zeros=Fa
         if hit_end.value and n0 < nrows:
             n0 = min(nrows, n0 * 4)
             continue
+        if hit_end.value and more_rows:
+            return None
         if nblks.value < 0:
             raise RuntimeError("deskew: some tracks have no transitions (is ntrks right?)")
         return [int(delays[t]) for t in range(hdr.ntrks)]
 
 
-def detect_density(hdr, rows, full, o, fe_factory, invert=False, log_path=None, evt_path=None, first_prefix_rows=1 << 22):
+def detect_density(hdr, rows, full, o, fe_factory, invert=False, log_path=None, evt_path=None, first_prefix_rows=1 << 22, more_rows=False):
     """Density detection (src/readtape.c:1656-1672) when the tape's header carries no bpi: a prefix of the resident tape
     is scanned with the front end in its bpi = 0 configuration (window of 8 samples, no AGC feedback), the host builds
     the histogram of transition distances from the first 9999 of them and picks the standard density.  NRZI only
     (for PE and GCR the reference's own pre-pass degenerates: with a zero clock estimate every track goes idle at each
-    peak, src/decoder.c:868,880; give bpi for those)."""
+    peak, src/decoder.c:868,880; give bpi for those).
+    more_rows: as in calibrate_deskew - `rows` is a prefix of a longer tape, and None means that the 9999 transitions are not all inside it."""
     if hdr.mode != tbin.MODE_NRZI:
         raise NotImplementedError("density detection is built for NRZI only: pass bpi")
     lib = _load_decode_lib()
@@ -232,6 +237,8 @@ def detect_density(hdr, rows, full, o, fe_factory, invert=False, log_path=None, 
         if hit_end.value and n0 < nrows and bpi.value >= 0:
             n0 = min(nrows, n0 * 4)
             continue
+        if hit_end.value and more_rows and bpi.value >= 0:
+            return None
         if bpi.value < 0:
             raise RuntimeError("density detection met a non-positive transition distance (or too many distinct ones): non-standard input, fatal in the reference too; please specify bpi")
         if bpi.value == 0:
@@ -433,9 +440,10 @@ def decode_tape_ww(hdr, rows, tap_path, log_path=None, order: str | None = None,
 I64MAX = (1 << 63) - 1
 
 
-def scan_fragment(fe, rows_with_halo, own_rows, lo, is_first, is_last, stream=None):
-    """Scans one fragment (async) -> a function that fetches (result, absolute bursts incl. the bounding one, stop_row or None)."""
-    res = fe.scan(rows_with_halo, row_base=lo, first_is_tape_start=is_first, own_rows=own_rows, stream=stream)
+def scan_fragment(fe, rows_with_halo, own_rows, lo, is_first, is_last, stream=None, raw=None):
+    """Scans one fragment (async) -> a function that fetches (result, absolute bursts incl. the bounding one, stop_row or None).
+    raw: FrontEnd.scan's - the fragment's rows are first thinned out of a raw window (-subsample)."""
+    res = fe.scan(rows_with_halo, row_base=lo, first_is_tape_start=is_first, own_rows=own_rows, stream=stream, raw=raw)
 
     def finish():
         res.fetch()
