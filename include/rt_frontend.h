@@ -159,10 +159,23 @@ int64_t rtfe_event_capacity(const rtfe_handle *h, int64_t nrows);
  * Time shards: row_base is the absolute index of d_rows[0] on the tape (used for times only; all rows in
  * the outputs are relative to d_rows[0]); first_is_tape_start says row 0 is a true restart point (the
  * start of the tape); own_rows <= nrows is the part of the slice this scan OWNS — rows
- * [own_rows, nrows) are the halo received from the right neighbour.  A burst is decoded here iff its
- * zone ends at or before own_rows; the last owned burst runs on into the halo up to the next zone's
- * restart row.  If the halo holds no further zone the last owned burst is flagged RTFE_F_TRUNCATED
- * (pass a longer halo).  own_rows == nrows: no halo (single GPU, or the last shard).
+ * [own_rows, nrows) are the halo received from the right neighbour.  Zones are found on whole groups of 64
+ * rows: a group is quiet iff it is complete and every sample of every track lies inside the quiet band, a
+ * zone is a maximal run of at least G quiet groups (G = the gap length in groups, rtfe_max_bursts(h, n) ==
+ * (n / 64) / G + 4), zone_first = 64 * its first group, zone_end = 64 * (its last group + 1).  The rows of an
+ * incomplete last group are never quiet, so a zone that ends with the tape ends at nrows rounded down to a
+ * multiple of 64 and zone_end <= nrows always.  A burst is decoded here iff its zone_end < own_rows + 64 G:
+ * a zone that reaches G groups or more past own_rows qualifies in the right neighbour's slice (whose row 0
+ * is own_rows) and is decoded there, one that ends earlier shows the neighbour too few quiet groups and
+ * stays here; the exact-start burst of row 0 (first_is_tape_start, and the slice does not begin with G quiet
+ * groups) is always owned.  The last owned burst runs on into the halo up to the next zone's restart row;
+ * that next burst's entry is written at bursts[*nbursts] as k_bursts made it (reset_sample = safe_last = -1,
+ * end_sample provisional); what lies behind it means nothing.  If the halo holds no further zone the last owned burst is
+ * flagged RTFE_F_TRUNCATED (pass a longer halo).  own_rows == nrows: no halo (single GPU, or the last shard).
+ * Event regions: event_cap = (int)((float)len * cap) + 64 in float32, len = the rows from zone_end - 256 (an
+ * exact-start burst: row 0) to the next table entry's zone_end (the last entry: nrows), cap = events_per_sample_cap;
+ * event_base = the sum, over the bursts in front, of a burst's nparmsets * ntrks regions rounded up to 64 events.  A burst whose regions would pass
+ * event_capacity gets event_cap = 0 and RTFE_F_EVENT_OVERFLOW; the bases behind it go on as if it had fitted.
  * Outputs (device): bursts[*nbursts] (owned bursts only), counts, events. */
 int rtfe_scan(rtfe_handle *h, const int16_t *d_rows, int64_t nrows, int64_t own_rows, int64_t row_base, int first_is_tape_start,
               void *d_workspace, size_t workspace_bytes,

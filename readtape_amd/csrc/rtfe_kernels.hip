@@ -272,7 +272,7 @@ __device__ __forceinline__ void br_emit(const BrWin &bw, long long w0, const u64
             rtfe_burst b = {};
             long long zf = c0 * kChunkRows;                          // first row of the zone (chunks are groups of 64 rows)
             long long ze = c1 * kChunkRows;                          // one past its last row
-            if (ze > nrows) ze = nrows & ~63ll;
+            if (ze > nrows) ze = nrows & ~63ll;                     // (never taken: only complete groups are quiet, so ze <= nrows & ~63 as it is - include/rt_frontend.h)
             b.zone_first = zf; b.zone_end = ze; b.reset_sample = -1; b.safe_last = -1;
             bursts[idx] = b; }
          ++idx; } } }
