@@ -47,35 +47,64 @@ class _All:
             f.result()
 
 
-def _prepasses(hdr, fd, off, nrows, nth, full, opts, cfgkw, deskew, prepass_rows, device):
-    """What the reference settles before its main pass (src/readtape.c:1656-1717), on a prefix of the file: the density of a header without one, then the
-    -deskew delays with that density - pipeline.detect_density / calibrate_deskew, which the resident decode runs on its whole tape.  -> cfgkw with what they
-    found ("bpi", "skew"); unchanged, and nothing read or launched, where neither is asked for.  off: the payload behind the skipped rows; nrows: used rows."""
+def _prepass_needs(hdr, cfgkw, deskew):
+    """(density to detect, delays to calibrate) - what the header and the caller's configuration leave open."""
     need_bpi = hdr.mode != tbin.MODE_GCR and not hdr.bpi > 0 and not cfgkw.get("bpi")
     need_skew = bool(deskew) and cfgkw.get("skew") is None and hdr.mode != tbin.MODE_PE      # "-deskew option is ignored for PE", src/readtape.c:1677
+    return need_bpi, need_skew
+
+
+def _settle(hdr, full, opts, cfgkw, need_bpi, need_skew, make_fe, run):
+    """The two pre-passes in the reference's order (src/readtape.c:1656-1717): the density, then the delays with that density -> cfgkw with "bpi" / "skew".
+    run(what, fn): calls fn(rows, more_rows) on the rows the caller has - the streaming reader's growing prefix, a rank's resident share - and returns
+    its answer (never None: an undecided pre-pass is the caller's to resolve or to refuse)."""
+    invert, find_zeros, differentiate = (bool(cfgkw.get(k, False)) for k in ("invert", "find_zeros", "differentiate"))
+
+    def options(bpi):
+        return pipeline._Options(mode=hdr.mode, ntrks=hdr.ntrks, bpi=bpi, ips=hdr.ips or 50.0, specified_parity=0 if opts.even_parity else 1, revparity=opts.revparity,
+                                 do_correction=int(opts.correct), find_zeros=int(find_zeros), do_differentiate=int(differentiate),
+                                 multiple_tries=int(opts.multiple_tries), tap_format=1, add_parity=0, verbose=int(opts.verbose))
+
+    cfgkw = dict(cfgkw)
+    if need_bpi:
+        cfgkw["bpi"] = run("density detection", lambda rows, more: pipeline.detect_density(
+            hdr, rows, full, options(0.0), make_fe, invert=invert, first_prefix_rows=max(1, int(rows.shape[0])), more_rows=more))
+    if need_skew:
+        rest = {k: v for k, v in cfgkw.items() if k not in ("invert", "find_zeros", "differentiate", "skew")}
+        bpi = frontend.FrontEndConfig.from_header(hdr, **({"bpi": cfgkw["bpi"]} if "bpi" in cfgkw else {})).bpi
+        cfgkw["skew"] = run("-deskew calibration", lambda rows, more: pipeline.calibrate_deskew(
+            hdr, rows, full, options(bpi), make_fe, invert=invert, find_zeros=find_zeros, differentiate=differentiate,
+            first_prefix_rows=max(1, int(rows.shape[0])), more_rows=more, **rest))
+    return cfgkw
+
+
+def _prepasses(hdr, fd, off, nrows, nth, full, opts, cfgkw, deskew, prepass_rows, device, fe_factory=None, backend=None, lib=None):
+    """What the reference settles before its main pass (src/readtape.c:1656-1717), on a prefix of the file: the density of a header without one, then the
+    -deskew delays with that density - pipeline.detect_density / calibrate_deskew, which the resident decode runs on its whole tape.  -> cfgkw with what they
+    found ("bpi", "skew"); unchanged, and nothing read or launched, where neither is asked for.  off: the payload behind the skipped rows; nrows: used rows.
+    fe_factory / backend / lib: the front ends, the memory and the library of the prefix (default: the GPU's; shard.decode_file_sharded hands its own on,
+    tests/cpu_emul's included - with a backend of the caller's the prefix is host arrays)."""
+    need_bpi, need_skew = _prepass_needs(hdr, cfgkw, deskew)
     if not (need_bpi or need_skew) or nrows <= 0:
         return cfgkw
     if need_bpi and hdr.mode != tbin.MODE_NRZI:
         pipeline.detect_density(hdr, None, full, None, None)      # (raises what the resident decode raises: density detection is NRZI's)
     import torch
     ntrks = hdr.ntrks
-    dev = torch.device(device)
-    be, lib, dlib = frontend.TorchBackend(device), frontend._load_library(), pipeline._load_decode_lib()
-    make_fe = lambda c: frontend.FrontEnd(c, device=device)
-    invert, find_zeros, differentiate = (bool(cfgkw.get(k, False)) for k in ("invert", "find_zeros", "differentiate"))
-
-    def options(bpi):
-        return pipeline._Options(mode=hdr.mode, ntrks=ntrks, bpi=bpi, ips=hdr.ips or 50.0, specified_parity=0 if opts.even_parity else 1, revparity=opts.revparity,
-                                 do_correction=int(opts.correct), find_zeros=int(find_zeros), do_differentiate=int(differentiate),
-                                 multiple_tries=int(opts.multiple_tries), tap_format=1, add_parity=0, verbose=int(opts.verbose))
+    on_host = backend is not None
+    be, lib, dlib = backend or frontend.TorchBackend(device), lib or frontend._load_library(), pipeline._load_decode_lib()
+    make_fe = fe_factory or (lambda c: frontend.FrontEnd(c, device=device))
 
     def prefix(want):
         """the used rows [0, want) on the device, cut at the end marker -> (rows, whether the tape goes on behind them)"""
-        host = torch.empty((want * nth, ntrks), dtype=torch.int16, pin_memory=True)
+        host = torch.empty((want * nth, ntrks), dtype=torch.int16, pin_memory=not on_host)
         if dlib.rt_read_mt(fd, host.numpy().ctypes.data, off, want * nth * 2 * ntrks, 4) != 0:
             raise IOError("short read")
-        d_raw = host.to(dev, non_blocking=True)
-        rows, d_mark = torch.empty((want, ntrks), dtype=torch.int16, device=dev), be.empty(16)
+        if on_host:
+            d_raw, rows = host.numpy(), torch.empty((want, ntrks), dtype=torch.int16).numpy()
+        else:
+            d_raw, rows = host.to(torch.device(device), non_blocking=True), torch.empty((want, ntrks), dtype=torch.int16, device=torch.device(device))
+        d_mark = be.empty(16)
         frontend.decimate_rows(lib, be, d_raw, want * nth, nth - 1, nth, rows, d_mark)      # (step 1: a copy and the end-of-data check)
         m = int(be.to_numpy(d_mark, np.int64)[0])
         used = want if m == np.iinfo(np.int64).max else min(want, m // nth)
@@ -94,17 +123,7 @@ def _prepasses(hdr, fd, off, nrows, nth, full, opts, cfgkw, deskew, prepass_rows
             del rows
             want = min(nrows, want * 4)                    # (None only with more rows behind the prefix: want < nrows)
 
-    cfgkw = dict(cfgkw)
-    if need_bpi:
-        cfgkw["bpi"] = run("density detection", lambda rows, more: pipeline.detect_density(
-            hdr, rows, full, options(0.0), make_fe, invert=invert, first_prefix_rows=max(1, int(rows.shape[0])), more_rows=more))
-    if need_skew:
-        rest = {k: v for k, v in cfgkw.items() if k not in ("invert", "find_zeros", "differentiate", "skew")}
-        bpi = frontend.FrontEndConfig.from_header(hdr, **({"bpi": cfgkw["bpi"]} if "bpi" in cfgkw else {})).bpi
-        cfgkw["skew"] = run("-deskew calibration", lambda rows, more: pipeline.calibrate_deskew(
-            hdr, rows, full, options(bpi), make_fe, invert=invert, find_zeros=find_zeros, differentiate=differentiate,
-            first_prefix_rows=max(1, int(rows.shape[0])), more_rows=more, **rest))
-    return cfgkw
+    return _settle(hdr, full, opts, cfgkw, need_bpi, need_skew, make_fe, run)
 
 
 def plan_windows(raw_rows, window_rows, halo_rows, subsample=1, skip=0, ramp=True):
