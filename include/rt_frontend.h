@@ -423,6 +423,32 @@ int    rtfe_csv_format_path(int64_t first_row, int64_t nrows, const rtfe_csv_for
 int    rtfe_csv_format(const int16_t *d_rows, int64_t first_row, int64_t nrows, const rtfe_csv_format_args *a,
                        void *d_text, size_t text_cap, void *d_scratch, size_t scratch_bytes, rtfe_csv_text *d_out, void *stream);
 
+/* ---- the interpreted text dump of a SIMH .tap image (the reference's -tapread, src/textfile.c and src/tapread.c), made on the device.  Handle-free.
+ * The image's bytes lie in device memory; its items - records, tape marks, the reader's messages, in file order - come from the host's reader (rt_tap_items,
+ * csrc/host/rt_textfile.h; the same 16 bytes an item) and are given twice: items on the host, where they are checked against image_bytes and counted, and
+ * d_items, the same table on the device, which the kernels read.  A window of a large image is a slice of the table.
+ * rtfe_text_format writes the BODY of the terse layout - per record the "%c%4d: " prefix ('!' in front of a record whose marker has the error bit), its lines
+ * of numbers and / or characters with seven blanks in front of every further line, "tape mark", the messages - byte for byte what the host writer
+ * (rt_text_record ...) puts between the three title lines and the trailer, which stay the host's.  Options as the reference's: numtype 0 none / 1 hex / 2 octal /
+ * 3 octal2, chartype 0 none / 1 BCD / 2 EBCDIC / 3 ASCII / 4 B5500 / 5 sixbit / 6 SDS / 7 SDSM / 8 flexo / 9 adage / 10 adagetape / 11 CDC / 12 Univac,
+ * linesize 4..400 (0: 32 with both types, otherwise 64), dataspace 0..400 (-1: 2 under octal2, otherwise 0), linefeed, ntrks (up to 7: two octal digits a byte).
+ * Refused with an error string: verbose != 0 (the decode path's layout: its block lines are host strings) and neither a number nor a character type (the list
+ * of block sizes is sequential and trivial: the host writes it).
+ * nlinefeeds: with linefeed, at least the number of 0x0a bytes in the items' data (the whole slice of the image may be counted); it sizes the scratch, and a
+ *   count that is too small sets RTFE_TEXT_SCRATCH_FULL: no text is written.  Ignored without linefeed.
+ * *d_out: bytes = the length of the whole body, lines, stretches (pieces of records between the linefeeds that break lines; without linefeed: the items).  A
+ *   body longer than text_cap sets RTFE_TEXT_FULL: the first text_cap bytes are written, nothing at or behind d_text + text_cap, and bytes is right all the
+ *   same.  rtfe_text_format_max_bytes always suffices (exact without linefeed unless ntrks <= 7 prints octal).  d_text 16-byte, d_scratch 8-byte aligned. */
+#define RTFE_TEXT_FULL 1
+#define RTFE_TEXT_SCRATCH_FULL 2
+typedef struct rtfe_text_options { int numtype, chartype, linesize, dataspace, linefeed, ntrks, verbose; } rtfe_text_options;
+typedef struct rtfe_text_item { uint64_t offset; uint32_t length; uint16_t kind, flag; } rtfe_text_item;      /* kind 0 record / 1 tape mark / 2 message (flag: which) */
+typedef struct rtfe_text_out { uint64_t bytes, lines, stretches; uint32_t flags, reserved; } rtfe_text_out;      /* 32 bytes */
+size_t rtfe_text_format_max_bytes(const rtfe_text_item *items, int64_t nitems, uint64_t nlinefeeds, const rtfe_text_options *o);        /* 0: refused */
+size_t rtfe_text_format_scratch_bytes(const rtfe_text_item *items, int64_t nitems, uint64_t nlinefeeds, const rtfe_text_options *o);
+int    rtfe_text_format(const void *d_image, uint64_t image_bytes, const rtfe_text_item *items, const rtfe_text_item *d_items, int64_t nitems, uint64_t nlinefeeds,
+                        const rtfe_text_options *o, void *d_text, size_t text_cap, void *d_scratch, size_t scratch_bytes, rtfe_text_out *d_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

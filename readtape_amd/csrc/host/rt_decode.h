@@ -195,6 +195,13 @@ struct rt_dec {
    void  (*on_transition)(struct rt_dec *d, struct rt_trk *t, int is_top, void *user);
    void  (*on_attempt)(struct rt_dec *d, void *user);
    void   *user;
+   /* the interpreted text file (-textfile; rt_textfile.c), reached through pointers so that the driver links without the writer:
+    * called where the reference calls txtfile_outputrecord / txtfile_tapemark (src/readtape.c:1246, 1171) */
+   void   *text;
+   const char *text_name;           /* logged when the first record or tape mark makes the file */
+   int     text_logged;
+   void  (*text_record)(void *text, const unsigned char *bytes, int length, int errs, int warnings, const char *head);
+   void  (*text_tapemark)(void *text, double timenow);
 };
 #define RT_PARM(d) ((d)->parmsets[(d)->parmset])
 

@@ -8,6 +8,7 @@
 #include <limits.h>
 #include <stdarg.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 
 static void rlog(struct rt_dec *d, const char *fmt, ...) {
@@ -57,9 +58,14 @@ void rt_tap_end(struct rt_dec *d) {   /* src/readtape.c:1885-1887: the end-of-me
    if (d->opt.tap_format && created && !d->no_tap_end) output_tap_marker(d, 0xffffffffu);
    if (d->outbase[0]) rt_close_output(d); }
 
+static void text_file_logged(struct rt_dec *d) {   /* the text file is made by what is first written to it (src/textfile.c:198) */
+   if (!d->text_logged && d->text_name) rlog(d, "creating file \"%s\"\n", d->text_name);
+   d->text_logged = 1; }
+
 void rt_got_tapemark(struct rt_dec *d) {   /* src/readtape.c:1160-1176 */
    ++d->numtapemarks;
    rlog(d, "  tapemark at time %.8lf, tap offset %lld, %d blocks written so far\n", d->timenow, d->numoutbytes, d->numblks);
+   if (d->text_tapemark) { text_file_logged(d); d->text_tapemark(d->text, d->timenow); }
    if (d->opt.tap_format) {
       if (!d->tapf) open_output(d);
       output_tap_marker(d, 0x00000000); }
@@ -95,7 +101,18 @@ static const char *format_block_errors(struct rt_dec *d, struct rt_results *resu
       if (result->ww_missing_clock) p += sprintf(p, ", missing clk"); }
    return buf; }
 
-void rt_got_datablock(struct rt_dec *d, int badblock) {   /* src/readtape.c:1212-1313 (no labels, no text file) */
+/* the block's line in the verbose text file (src/textfile.c:246-249) and its data without the parity bit */
+static void text_datablock(struct rt_dec *d, struct rt_results *result, int length) {
+   char head[480], errs[400];
+   unsigned char *bytes = (unsigned char *)malloc((size_t)length + 1);
+   if (!bytes) return;
+   for (int i = 0; i < length; ++i) bytes[i] = (unsigned char)(d->data[i] >> 1);
+   snprintf(head, sizeof head, "block %d: %d bytes at time %.8lf, %s", d->numblks + 1, length, d->timenow, format_block_errors(d, result, errs));
+   text_file_logged(d);
+   d->text_record(d->text, bytes, length, result->errcount, result->warncount, head);
+   free(bytes); }
+
+void rt_got_datablock(struct rt_dec *d, int badblock) {   /* src/readtape.c:1212-1313 (no labels) */
    struct rt_results *result = &d->results[d->parmset];
    int length = result->minbits;
    if (length > 0) {
@@ -120,6 +137,7 @@ void rt_got_datablock(struct rt_dec *d, int badblock) {   /* src/readtape.c:1212
                if (d->tapf) fwrite(&zero, 1, 1, d->tapf);
                d->numoutbytes += 1; }
             output_tap_marker(d, (uint32_t)length | errflag); }
+         if (d->text_record) text_datablock(d, result, length);
          if (result->errcount != 0) ++d->numblks_err;
          if (result->warncount != 0) ++d->numblks_warn;
          if (d->opt.verbose || d->numblks == 0 || result->errcount > 0 || result->warncount > 0) {

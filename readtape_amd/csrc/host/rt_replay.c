@@ -358,6 +358,28 @@ int rt_replay_readblock(void *ctx, int retry) {
    if (!retry) rp->d->lines_in += (rp->pos - from) + (more ? 0 : 1);
    return more; }
 
+/* ---- the text file of the next decode (-textfile): asked for by rt_replay_set_text on the calling thread, taken by the run that
+ * processes blocks (not by a pre-pass), closed with its trailer when that run ends ---- */
+static __thread struct { int set; rt_text_options o; char base[1024], created[64]; } g_text_request;
+void rt_replay_set_text(const rt_text_options *o, const char *base, const char *created) {
+   g_text_request.set = 0;
+   if (!o || !base) return;
+   g_text_request.o = *o;
+   snprintf(g_text_request.base, sizeof g_text_request.base, "%s", base);
+   snprintf(g_text_request.created, sizeof g_text_request.created, "%s", created ? created : "");
+   g_text_request.set = 1; }
+static void text_record_hook(void *t, const unsigned char *bytes, int length, int errs, int warnings, const char *head) {
+   rt_text_record((struct rt_textfile *)t, bytes, length, errs, warnings, head); }
+static void text_tapemark_hook(void *t, double timenow) { rt_text_tapemark((struct rt_textfile *)t, timenow); }
+static struct rt_textfile *text_attach(struct rt_dec *d) {
+   if (!g_text_request.set) return NULL;
+   g_text_request.set = 0;
+   g_text_request.o.ntrks = d->opt.ntrks;
+   struct rt_textfile *t = rt_text_new(g_text_request.base, &g_text_request.o, 0, g_text_request.created[0] ? g_text_request.created : NULL);
+   if (!t) return NULL;
+   d->text = t; d->text_name = rt_text_filename(t); d->text_record = text_record_hook; d->text_tapemark = text_tapemark_hook;
+   return t; }
+
 /* prepass != NULL: run the -deskew pre-pass instead of the decode (no .tap); append: keep what is already in the log
  * and event-dump files (the decode that follows a pre-pass continues both, as the reference's single run does) */
 struct deskew_out { int *delays; int *nblks; int *hit_end; float *bpi, *implied; };
@@ -397,7 +419,10 @@ static int replay_any(const struct rt_options *opt, const struct rt_parms *parms
    int ok = 1;
    if (prepass && prepass->bpi) *prepass->bpi = rt_density_prepass(d, &rd, prepass->implied, prepass->nblks, prepass->hit_end);
    else if (prepass) *prepass->nblks = rt_deskew_prepass(d, &rd, prepass->delays, prepass->hit_end);
-   else ok = rt_process_blocks(d, &rd, 0x7fffffff);
+   else {
+      struct rt_textfile *text = text_attach(d);
+      ok = rt_process_blocks(d, &rd, 0x7fffffff);
+      if (text) { d->text = NULL; d->text_record = NULL; d->text_tapemark = NULL; rt_text_close(text, 1); } }      /* src/readtape.c:1886 */
    if (in_name && !prepass) rt_write_summary(d, in_name, difftime(time(NULL), (time_t)wall0));
    if (stats) {
       stats->attempts = rp.attempts; stats->exact_scans = rp.exact_scans; stats->chained = rp.chained;
@@ -693,7 +718,9 @@ int rt_replay_run_ww_detector(const struct rt_options *opt, const struct rt_parm
       else {
          ww_rewind_state(rp.ww_state, wide, o.ntrks, d, delays);
          if (delays_out) memcpy(delays_out, delays, sizeof(int) * (size_t)o.ntrks); } }
+   struct rt_textfile *text = prepass_failed ? NULL : text_attach(d);
    const int ok = prepass_failed ? 0 : rt_process_blocks(d, &rd, 0x7fffffff);
+   if (text) { d->text = NULL; d->text_record = NULL; d->text_tapemark = NULL; rt_text_close(text, 1); }
    if (in_name) rt_write_summary(d, in_name, difftime(time(NULL), (time_t)wall0));
    if (stats) {
       memset(stats, 0, sizeof *stats);

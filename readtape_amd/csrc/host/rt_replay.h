@@ -3,6 +3,7 @@
 #define RT_REPLAY_H
 #include "rt_decode.h"
 #include "rt_frontend.h"
+#include "rt_textfile.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -121,6 +122,9 @@ int rt_replay_run_after_deskew(const struct rt_options *opt, const struct rt_par
                   const rtfe_burst *bursts, int64_t nbursts, const uint32_t *counts, const rtfe_event *events,
                   rt_exact_fn exact, rt_exact_free_fn exact_free, void *user,
                   const char *tap_path, const char *log_path, const char *evt_path, struct rt_replay_stats *stats);
+/* -textfile: the next decode this thread starts (rt_replay_run, _run_named, _run_after_deskew, _run_ww, _run_ww_detector) writes the interpreted text
+ * file of <base> in the verbose layout beside its .tap; o->ntrks is taken from the decode.  o == NULL takes the request back. */
+void rt_replay_set_text(const rt_text_options *o, const char *base, const char *created);
 
 #ifdef __cplusplus
 }

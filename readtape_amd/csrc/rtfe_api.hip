@@ -25,6 +25,7 @@
 #include "rtfe_pack.hip"
 #include "rtfe_csv.hip"
 #include "rtfe_csvout.hip"
+#include "rtfe_textfile.hip"
 
 namespace rtfe {
 __global__ void k_setup_exact(rtfe_burst *burst, BurstScratch *scratch, long long reset_row, long long end_row,
@@ -1238,3 +1239,118 @@ extern "C" int rtfe_csv_format(const int16_t *d_rows, int64_t first_row, int64_t
       hipLaunchKernelGGL(k_csvout_scan, dim3(1), dim3(kCoScanThreads), 0, st, (uint32_t)nwg, sums, (long long)nrows, (unsigned long long)text_cap, d_out);
       if (nwg) hipLaunchKernelGGL(k_csvout_format<false>, dim3((unsigned)nwg), dim3(kCoWave), 0, st, k); }
    return launch_check("rtfe_csv_format"); }
+
+// ---- a .tap image -> the interpreted text's body on the device (include/rt_frontend.h; kernels in rtfe_textfile.hip) ----
+struct TxPlan {
+   rt_text_options o;
+   int doboth, narrow, lse, lines, maxline;
+   uint16_t tail[kTxTail];
+   unsigned long long max_stretches, max_lines, max_batches, max_bytes;
+   size_t w_cnt, w_st, w_lines, w_base;      // the scratch's parts, in 8-byte words
+};
+
+// a line of n bytes behind its prefix (src/textfile.c:180-188, 260-275): the numbers with their -dataspace blanks, then - with a character type as well - the
+// blanks that stand for the bytes the line lacks, two more without -dataspace, and a character a byte; '\n'
+static int tx_tail(const rt_text_options &o, bool doboth, bool narrow, int n) {
+   if (o.numtype == RT_NUM_NONE) return n + 1;
+   const int alone = narrow ? 2 : 3;
+   int len = o.numtype == RT_NUM_HEX ? 2 * n : o.numtype == RT_NUM_OCTAL ? alone * n : 6 * (n / 2) + (n & 1) * alone;
+   if (o.dataspace > 0) {
+      if (o.numtype != RT_NUM_OCTAL2) len += n / o.dataspace;
+      else { for (int j = 2; j <= n; j += 2) len += j % o.dataspace == 0; if ((n & 1) && n % o.dataspace == 0) ++len; } }
+   if (doboth) {
+      const int missing = o.linesize - n;
+      const int blanks = (o.dataspace ? missing / o.dataspace : 0) + missing * (o.numtype == RT_NUM_HEX || narrow ? 2 : 3);
+      len += (blanks > 0 ? blanks : 0) + (o.dataspace == 0 ? 2 : 0) + n; }
+   return len + 1; }
+
+static int tx_plan(const char *who, const rtfe_text_item *items, int64_t nitems, uint64_t image_bytes, uint64_t nlinefeeds, const rtfe_text_options *in, TxPlan *p) {
+   if (!in || (!items && nitems > 0)) return fail(-1, "%s: null argument", who);
+   if (nitems < 0 || nitems > 0x7fffffffll) return fail(-34, "%s: %lld items are more than a launch takes", who, (long long)nitems);
+   const rt_text_options raw = { in->numtype, in->chartype, in->linesize, in->dataspace, in->linefeed, in->ntrks };
+   const int bad = rt_text_resolve(&raw, &p->o);
+   if (bad) return fail(-50, "%s: text option %d (1 number type, 2 character type, 3 linesize, 4 dataspace) is out of range", who, bad);
+   if (in->verbose) return fail(-51, "%s: the verbose layout's block lines are the host's strings: the decode path writes its text on the host", who);
+   if (p->o.numtype == RT_NUM_NONE && p->o.chartype == RT_CHAR_NONE)
+      return fail(-52, "%s: without a number or a character type the text is a list of block sizes, which is sequential: the host writes it", who);
+   p->doboth = p->o.numtype != RT_NUM_NONE && p->o.chartype != RT_CHAR_NONE;
+   p->narrow = p->o.ntrks <= 7;
+   p->lse = p->o.numtype == RT_NUM_OCTAL2 ? (p->o.linesize + 1) & ~1 : p->o.linesize;
+   int tailmax = 0;
+   for (int n = 0; n < kTxTail; ++n) {
+      const int t = n <= p->lse ? tx_tail(p->o, p->doboth, p->narrow, n) : 0;
+      p->tail[n] = (uint16_t)t;
+      const int wide = !p->narrow ? 0 : p->o.numtype == RT_NUM_OCTAL ? n : p->o.numtype == RT_NUM_OCTAL2 ? (n & 1) : 0;
+      if (t + wide > tailmax) tailmax = t + wide; }
+   p->maxline = 9 + tailmax;
+   if (p->maxline < 40) p->maxline = 40;                                       // (a message line)
+   p->lines = (kTxLds - 16) / p->maxline < kTxWave ? (kTxLds - 16) / p->maxline : kTxWave;
+   unsigned long long lines = 0, bytes = 0;
+   const unsigned long long full = 7ull + p->tail[p->lse];
+   for (int64_t i = 0; i < nitems; ++i) {
+      const rtfe_text_item &it = items[i];
+      if (it.kind == RT_TAP_MARK) { ++lines; bytes += strlen(RT_TAP_MARK_TEXT); continue; }
+      if (it.kind == RT_TAP_MESSAGE) {
+         if (it.flag > 1) return fail(-53, "%s: item %lld: no message %d", who, (long long)i, (int)it.flag);
+         ++lines; bytes += strlen(rt_tap_messages[it.flag]); continue; }
+      if (it.kind != RT_TAP_RECORD) return fail(-53, "%s: item %lld is of kind %d", who, (long long)i, (int)it.kind);
+      if (it.length < 1 || it.length >= RT_TEXT_MAXBLOCK) return fail(-54, "%s: item %lld: a record of %u bytes", who, (long long)i, it.length);
+      if (it.offset > image_bytes || image_bytes - it.offset < it.length) return fail(-55, "%s: item %lld lies outside the image", who, (long long)i);
+      const unsigned long long nl = (it.length + (unsigned)p->lse - 1) / (unsigned)p->lse, last = it.length - (nl - 1) * (unsigned)p->lse;
+      lines += nl;
+      bytes += (it.length < 10000u ? 7 : it.length < 100000u ? 8 : 9) + (nl - 1) * full + p->tail[last];
+      if (p->narrow && p->o.numtype == RT_NUM_OCTAL) bytes += it.length; else if (p->narrow && p->o.numtype == RT_NUM_OCTAL2) bytes += 1; }
+   const unsigned long long extra = p->o.linefeed ? nlinefeeds + (unsigned long long)nitems : 0;      // a linefeed adds a stretch, a stretch at most a line
+   p->max_stretches = (unsigned long long)nitems + extra;
+   p->max_lines = lines + extra;
+   p->max_batches = (p->max_lines + (unsigned)p->lines - 1) / (unsigned)p->lines;
+   p->max_bytes = bytes + extra * (unsigned long long)p->maxline;
+   p->w_cnt = p->o.linefeed ? (size_t)nitems + 1 : 0;
+   p->w_st = p->o.linefeed ? (size_t)p->max_stretches : 0;
+   p->w_lines = (size_t)p->max_stretches + 1;
+   p->w_base = (size_t)p->max_batches + 1;
+   return 0; }
+
+extern "C" size_t rtfe_text_format_max_bytes(const rtfe_text_item *items, int64_t nitems, uint64_t nlinefeeds, const rtfe_text_options *o) {
+   TxPlan p;
+   return tx_plan("rtfe_text_format_max_bytes", items, nitems, UINT64_MAX, nlinefeeds, o, &p) ? 0 : (size_t)p.max_bytes; }
+extern "C" size_t rtfe_text_format_scratch_bytes(const rtfe_text_item *items, int64_t nitems, uint64_t nlinefeeds, const rtfe_text_options *o) {
+   TxPlan p;
+   return tx_plan("rtfe_text_format_scratch_bytes", items, nitems, UINT64_MAX, nlinefeeds, o, &p) ? 0 : (p.w_cnt + p.w_st + p.w_lines + p.w_base) * 8 + 16; }
+
+extern "C" int rtfe_text_format(const void *d_image, uint64_t image_bytes, const rtfe_text_item *items, const rtfe_text_item *d_items, int64_t nitems, uint64_t nlinefeeds,
+                                const rtfe_text_options *o, void *d_text, size_t text_cap, void *d_scratch, size_t scratch_bytes, rtfe_text_out *d_out, void *stream) {
+   static_assert(sizeof(rtfe_text_item) == sizeof(rt_tap_item) && sizeof(rtfe_text_item) == 16, "one item layout");
+   if (!d_image || !d_items || !d_text || !d_scratch || !d_out) return fail(-1, "rtfe_text_format: null argument");
+   TxPlan p;
+   const int rc = tx_plan("rtfe_text_format", items, nitems, image_bytes, nlinefeeds, o, &p);
+   if (rc) return rc;
+   if (((uintptr_t)d_text & 15) != 0) return fail(-31, "rtfe_text_format: d_text must be 16-byte aligned");
+   if (((uintptr_t)d_scratch & 7) != 0 || scratch_bytes < (p.w_cnt + p.w_st + p.w_lines + p.w_base) * 8 + 16) return fail(-32, "rtfe_text_format: scratch too small or misaligned");
+   hipStream_t st = (hipStream_t)stream;
+   TxArgs k;
+   k.image = reinterpret_cast<const unsigned char *>(d_image); k.items = d_items; k.nitems = nitems;
+   k.numtype = p.o.numtype; k.doboth = p.doboth; k.linesize = p.o.linesize; k.lse = p.lse; k.dataspace = p.o.dataspace; k.linefeed = p.o.linefeed; k.narrow = p.narrow;
+   k.lines = p.lines; k.max_stretches = p.max_stretches; k.max_batches = p.max_batches;
+   k.cnt = reinterpret_cast<unsigned long long *>(d_scratch); k.st = k.cnt + p.w_cnt; k.lines_v = k.st + p.w_st; k.base = k.lines_v + p.w_lines;
+   k.out_bytes = reinterpret_cast<unsigned long long *>(&d_out->bytes); k.out_lines = reinterpret_cast<unsigned long long *>(&d_out->lines);
+   k.out_stretches = reinterpret_cast<unsigned long long *>(&d_out->stretches); k.out_flags = &d_out->flags;
+   k.text = reinterpret_cast<unsigned char *>(d_text); k.text_cap = text_cap;
+   memcpy(k.tail, p.tail, sizeof k.tail);
+   rt_text_char_table(p.o.chartype, k.table);
+   if (hipMemsetAsync(d_out, 0, sizeof(rtfe_text_out), st) != hipSuccess) return fail(-30, "rtfe_text_format: hipMemsetAsync failed");
+   if (nitems == 0) return launch_check("rtfe_text_format");
+   if (p.o.linefeed) {
+      hipLaunchKernelGGL(k_tx_stretch<false>, dim3((unsigned)nitems), dim3(kTxWave), 0, st, k);
+      hipLaunchKernelGGL(k_tx_scan, dim3(1), dim3(kTxScanThreads), 0, st, k.cnt, (unsigned long long)nitems, (const unsigned long long *)nullptr, 1ull, (unsigned long long)nitems,
+                         k.out_stretches, p.max_stretches, k.out_flags, (uint32_t)RTFE_TEXT_SCRATCH_FULL);
+      hipLaunchKernelGGL(k_tx_stretch<true>, dim3((unsigned)nitems), dim3(kTxWave), 0, st, k); }
+   hipLaunchKernelGGL(k_tx_measure, dim3((unsigned)((p.max_stretches + 255) / 256)), dim3(256), 0, st, k);
+   hipLaunchKernelGGL(k_tx_scan, dim3(1), dim3(kTxScanThreads), 0, st, k.lines_v, (unsigned long long)nitems, p.o.linefeed ? (const unsigned long long *)k.out_stretches : nullptr, 1ull,
+                      p.max_stretches, k.out_lines, ~0ull, (uint32_t *)nullptr, 0u);
+   const unsigned grid = (unsigned)(p.max_batches < (unsigned long long)kTxMaxGrid ? p.max_batches : (unsigned long long)kTxMaxGrid);
+   hipLaunchKernelGGL(k_tx_len, dim3(grid), dim3(kTxWave), 0, st, k);
+   hipLaunchKernelGGL(k_tx_scan, dim3(1), dim3(kTxScanThreads), 0, st, k.base, 0ull, (const unsigned long long *)k.out_lines, (unsigned long long)p.lines, p.max_batches,
+                      k.out_bytes, (unsigned long long)text_cap, k.out_flags, (uint32_t)RTFE_TEXT_FULL);
+   hipLaunchKernelGGL(k_tx_format, dim3(grid), dim3(kTxWave), 0, st, k);
+   return launch_check("rtfe_text_format"); }

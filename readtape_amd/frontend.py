@@ -272,7 +272,12 @@ def _load_library(path=None):
         lib.rtfe_csv_format_scratch_bytes.argtypes = [C.c_int64]; lib.rtfe_csv_format_scratch_bytes.restype = C.c_size_t
         lib.rtfe_csv_format_path.argtypes = [C.c_int64, C.c_int64, C.c_void_p]
         lib.rtfe_csv_format.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
-    if hasattr(lib, "rtfe_decimate_rows"):                 # -subsample on a raw window (decimate_rows; ingest.decode_file_streaming)
+    if hasattr(lib, "rtfe_text_format"):                   # a .tap image -> the interpreted text on the device (textfile.write_text_device)
+        lib.rtfe_text_format_max_bytes.argtypes = [C.c_void_p, C.c_int64, C.c_uint64, C.c_void_p]; lib.rtfe_text_format_max_bytes.restype = C.c_size_t
+        lib.rtfe_text_format_scratch_bytes.argtypes = [C.c_void_p, C.c_int64, C.c_uint64, C.c_void_p]; lib.rtfe_text_format_scratch_bytes.restype = C.c_size_t
+        lib.rtfe_text_format.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                         C.c_void_p, C.c_void_p]
+    if hasattr(lib, "rtfe_decimate_rows"):                # -subsample on a raw window (decimate_rows; ingest.decode_file_streaming)
         lib.rtfe_decimate_span_rows.argtypes = [C.c_int]; lib.rtfe_decimate_span_rows.restype = C.c_int64
         lib.rtfe_decimate_rows.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     if lib.rtfe_abi_version() != 6:

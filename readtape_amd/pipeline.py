@@ -87,6 +87,7 @@ class DecodeOptions:
     even_parity: bool = False         # -even
     revparity: int = 0                # -revparity=n
     verbose: bool = True              # -v
+    add_parity: bool = False          # -addparity: the parity bit goes into the data bytes as their top bit (up to 8 tracks)
     nparmsets: int | None = None      # how many built-in parameter sets to scan (default: 1, or all with -m)
 
 
@@ -257,17 +258,22 @@ class ReferenceFatal(RuntimeError):
 def decode_tape(hdr, rows, tap_path, log_path=None, opts: DecodeOptions | None = None, fe_factory=None,
                 skew=None, invert=False, parms_text: str | None = None, find_zeros=False, evt_path=None, differentiate=False,
                 subsample: int = 1, deskew: bool = False, deskew_prefix_rows: int = 1 << 22, trkorder: str | None = None,
-                out_base: str | None = None, in_name: str | None = None, tap_format: bool = True, fluxdir: str = "neg", reverse: bool = False):
+                out_base: str | None = None, in_name: str | None = None, tap_format: bool = True, fluxdir: str = "neg", reverse: bool = False,
+                textfile=None, created=None):
     """Decodes one tape; returns (stats dict, ScanResult).  `fe_factory(cfg)` builds the front end
     (default: the GPU one; tests/cpu_emul passes the emulated library).
     Output: tap_path = one SIMH .tap file; or out_base = the reference's own naming - <out_base>.tap, or with tap_format=False
     the numbered <out_base>.NNN.bin data files, one per tape file (src/readtape.c:1091-1111) - with the files' creation/closing
-    and the end-of-run summary (src/readtape.c:2021-2044; in_name = the input's name in it) in the log."""
+    and the end-of-run summary (src/readtape.c:2021-2044; in_name = the input's name in it) in the log.
+    textfile = textfile.TextOptions(...): the reference's -textfile - the interpreted text of every block, in the verbose layout, in
+    textfile.text_name(out_base or tap_path without its extension, textfile); created: the date in its title (textfile.write_text)."""
     opts = opts or DecodeOptions()
+    if opts.add_parity and hdr.ntrks >= 9:
+        raise ValueError(f"-addparity is not allowed with ntrks={hdr.ntrks}")      # src/readtape.c:1645
     if hdr.mode == tbin.MODE_WW:                                           # one chain per tape, detector state handed back and forth: its own path
         st = decode_tape_ww(hdr, rows, tap_path, log_path=log_path, order=trkorder, verbose=opts.verbose, evt_path=evt_path, fe_factory=fe_factory,
                             invert=invert, out_base=out_base, in_name=in_name, deskew=deskew, fluxdir=fluxdir, reverse=reverse,      # (-fluxdir, -reverse: Whirlwind only)
-                            find_zeros=find_zeros, differentiate=differentiate)
+                            find_zeros=find_zeros, differentiate=differentiate, textfile=textfile, created=created)
         return st, None
     lib = _load_decode_lib()
     if trkorder:                                                           # -order= wins over the header's TBINORD extension (src/readtape.c:1346-1355)
@@ -296,14 +302,14 @@ def decode_tape(hdr, rows, tap_path, log_path=None, opts: DecodeOptions | None =
     if hdr.mode != tbin.MODE_GCR and not hdr.bpi > 0:                   # density unknown: estimate it from the first transitions
         o_probe = _Options(mode=mode, ntrks=hdr.ntrks, bpi=0.0, ips=hdr.ips or 50.0, specified_parity=0 if opts.even_parity else 1,
                            revparity=opts.revparity, do_correction=int(opts.correct), find_zeros=int(find_zeros), do_differentiate=int(differentiate),
-                           multiple_tries=int(opts.multiple_tries), tap_format=1, add_parity=0, verbose=int(opts.verbose))
+                           multiple_tries=int(opts.multiple_tries), tap_format=1, add_parity=int(opts.add_parity), verbose=int(opts.verbose))
         bpi_kw = {"bpi": detect_density(hdr, rows, full, o_probe, fe_factory, invert=invert, log_path=log_path, evt_path=evt_path,
                                         first_prefix_rows=deskew_prefix_rows)}
         detected = True
     cfg = frontend.FrontEndConfig.from_header(hdr, parmsets=frontend_parmsets(full), skew=skew, invert=invert, find_zeros=find_zeros, differentiate=differentiate, **bpi_kw)
     o = _Options(mode=mode, ntrks=hdr.ntrks, bpi=cfg.bpi, ips=cfg.ips, specified_parity=0 if opts.even_parity else 1,
                  revparity=opts.revparity, do_correction=int(opts.correct), find_zeros=int(find_zeros), do_differentiate=int(differentiate),
-                 multiple_tries=int(opts.multiple_tries), tap_format=1, add_parity=0, verbose=int(opts.verbose))
+                 multiple_tries=int(opts.multiple_tries), tap_format=1, add_parity=int(opts.add_parity), verbose=int(opts.verbose))
     calibrated = deskew and skew is None and mode != tbin.MODE_PE        # "-deskew option is ignored for PE", src/readtape.c:1677
     if calibrated:
         skew = calibrate_deskew(hdr, rows, full, o, fe_factory, invert=invert, find_zeros=find_zeros, differentiate=differentiate,
@@ -315,11 +321,12 @@ def decode_tape(hdr, rows, tap_path, log_path=None, opts: DecodeOptions | None =
 
     o = _Options(mode=mode, ntrks=hdr.ntrks, bpi=cfg.bpi, ips=cfg.ips, specified_parity=0 if opts.even_parity else 1,
                  revparity=opts.revparity, do_correction=int(opts.correct), find_zeros=int(find_zeros), do_differentiate=int(differentiate),
-                 multiple_tries=int(opts.multiple_tries), tap_format=int(tap_format), add_parity=0, verbose=int(opts.verbose))
+                 multiple_tries=int(opts.multiple_tries), tap_format=int(tap_format), add_parity=int(opts.add_parity), verbose=int(opts.verbose))
     parr = (_Parms * len(full))(*full)
     W = (C.c_int * len(full))(*fe.widths)
     exact, free, keep = _exact_callbacks(fe, rows, hdr.ntrks, fe_factory)
 
+    _request_text(lib, textfile, out_base, tap_path, created)
     st = _Stats()
     bursts = np.ascontiguousarray(res.bursts)
     counts = np.ascontiguousarray(res.counts)
@@ -355,9 +362,22 @@ def decode_tape(hdr, rows, tap_path, log_path=None, opts: DecodeOptions | None =
 FLUX = {"neg": 0, "pos": 1, "auto": 2}
 
 
+def _request_text(lib, opts, out_base, tap_path, created):
+    """-textfile for the decode that is about to start on this thread (rt_replay_set_text)."""
+    if opts is None:
+        return
+    from . import textfile as tf
+    base = out_base or (os.path.splitext(tap_path)[0] if tap_path else None)
+    if base is None:
+        raise ValueError("textfile: give out_base or tap_path, the text file is named after it")
+    lib.rt_replay_set_text.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p]
+    o = tf.c_options(opts)
+    lib.rt_replay_set_text(C.byref(o), os.fsencode(base), tf._created(created))
+
+
 def decode_tape_ww(hdr, rows, tap_path, log_path=None, order: str | None = None, fluxdir: str = "neg", reverse: bool = False, verbose: bool = True,
                    evt_path=None, fe_factory=None, invert=False, chunk_rows: int = 4096, out_base=None, in_name=None, deskew: bool = False,
-                   find_zeros: bool = False, differentiate: bool = False):
+                   find_zeros: bool = False, differentiate: bool = False, textfile=None, created=None):
     """Decodes a Whirlwind tape (6 tracks, 100 BPI; mode WW in the header or by the caller).  order = the heads' roles (-order=CMLcml,
     default: the header's TBINORD string); fluxdir neg / pos / auto.  The device detector keeps its state across block attempts, so
     the host replay fetches its events in chunks and hands the state back in (rtfe_ww_scan).  deskew: the reference's
@@ -408,6 +428,7 @@ def decode_tape_ww(hdr, rows, tap_path, log_path=None, order: str | None = None,
             return 2
 
     cb = _WW_SCAN_FN(scan)
+    _request_text(lib, textfile, out_base, tap_path, created)
     st = _Stats()
     init = fe.ww_initial_state()
     delays = (C.c_int * hdr.ntrks)()
@@ -468,7 +489,7 @@ def decode_fragment(hdr, cfg, fe, res, rows_with_halo, lo, start_row, stop_row, 
     lib = _load_decode_lib()
     o = _Options(mode=hdr.mode, ntrks=hdr.ntrks, bpi=cfg.bpi, ips=cfg.ips, specified_parity=0 if opts.even_parity else 1,
                  revparity=opts.revparity, do_correction=int(opts.correct), find_zeros=int(cfg.find_zeros), do_differentiate=int(cfg.differentiate),
-                 multiple_tries=int(opts.multiple_tries), tap_format=1, add_parity=0, verbose=int(opts.verbose))
+                 multiple_tries=int(opts.multiple_tries), tap_format=1, add_parity=int(opts.add_parity), verbose=int(opts.verbose))
     parr = (_Parms * len(full))(*full)
     W = (C.c_int * len(full))(*fe.widths)
     exact, free, keep = _exact_callbacks(fe, rows_with_halo, hdr.ntrks, fe_factory, lock=exact_lock)
@@ -496,7 +517,7 @@ def decode_fragments(hdr, cfg, fe, res, rows_with_halo, lo, start_rows, stop_row
     lib = _load_decode_lib()
     o = _Options(mode=hdr.mode, ntrks=hdr.ntrks, bpi=cfg.bpi, ips=cfg.ips, specified_parity=0 if opts.even_parity else 1,
                  revparity=opts.revparity, do_correction=int(opts.correct), find_zeros=int(cfg.find_zeros), do_differentiate=int(cfg.differentiate),
-                 multiple_tries=int(opts.multiple_tries), tap_format=1, add_parity=0, verbose=int(opts.verbose))
+                 multiple_tries=int(opts.multiple_tries), tap_format=1, add_parity=int(opts.add_parity), verbose=int(opts.verbose))
     parr = (_Parms * len(full))(*full)
     W = (C.c_int * len(full))(*fe.widths)
     exact, free, keep = _exact_callbacks(fe, rows_with_halo, hdr.ntrks, fe_factory, lock=exact_lock)
