@@ -202,6 +202,8 @@ struct rt_dec {
    int     text_logged;
    void  (*text_record)(void *text, const unsigned char *bytes, int length, int errs, int warnings, const char *head);
    void  (*text_tapemark)(void *text, double timenow);
+   /* IBM standard labels (src/ibmlabels.c; rt_driver_set_run): label blocks are logged, and without -tap absorbed, the data files named after HDR1 */
+   int     labels, hdr1_seen;
 };
 #define RT_PARM(d) ((d)->parmsets[(d)->parmset])
 
@@ -275,6 +277,9 @@ struct rt_reader {
    void *ctx;
 };
 int rt_process_blocks(struct rt_dec *d, struct rt_reader *r, int blklimit);   /* returns 1 if all blocks clean */
+/* For the next rt_process_blocks this thread starts (then forgotten, like rt_replay_set_text): labels != 0 turns the IBM label
+ * handling on (the reference's default, off with -nolabels); blklimit >= 0 is the reference's -blklimit=n, < 0 none. */
+void rt_driver_set_run(int labels, int blklimit);
 
 /* ---- the -deskew pre-pass (src/readtape.c:1675-1717, NRZI and GCR): decodes the first blocks with no deskew while the
  * decoders record where each track's transitions fall, then turns the per-track averages into delays (in samples).

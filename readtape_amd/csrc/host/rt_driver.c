@@ -41,10 +41,12 @@ void rt_close_output(struct rt_dec *d) {
    char cb[32];
    rlog(d, "%s was closed at time %.8lf after %s data bytes were extracted from %d blocks\n", d->outname, d->timenow, commas(d->numfilebytes, cb), d->numfileblks); }
 
-static void open_output(struct rt_dec *d) {
+/* labelled != NULL: the name an HDR1 label gave the file (src/readtape.c:1094-1097) */
+static void open_output(struct rt_dec *d, const char *labelled) {
    if (!d->outbase[0]) return;
    if (d->tapf) rt_close_output(d);
-   if (d->opt.tap_format) snprintf(d->outname, sizeof d->outname, "%s.tap", d->outbase);
+   if (labelled) snprintf(d->outname, sizeof d->outname, "%s.bin", labelled);
+   else if (d->opt.tap_format) snprintf(d->outname, sizeof d->outname, "%s.tap", d->outbase);
    else snprintf(d->outname, sizeof d->outname, "%s.%03d.bin", d->outbase, d->numfiles + 1);
    rlog(d, "creating file \"%s\"\n", d->outname);
    d->tapf = fopen(d->outname, "wb");
@@ -67,9 +69,10 @@ void rt_got_tapemark(struct rt_dec *d) {   /* src/readtape.c:1160-1176 */
    rlog(d, "  tapemark at time %.8lf, tap offset %lld, %d blocks written so far\n", d->timenow, d->numoutbytes, d->numblks);
    if (d->text_tapemark) { text_file_logged(d); d->text_tapemark(d->text, d->timenow); }
    if (d->opt.tap_format) {
-      if (!d->tapf) open_output(d);
+      if (!d->tapf) open_output(d, NULL);
       output_tap_marker(d, 0x00000000); }
-   else rt_close_output(d); }                 /* plain data files: a tapemark ends the file (no label processing here) */
+   else if (!d->hdr1_seen) rt_close_output(d);      /* plain data files: a tapemark ends the file, unless an HDR1 label named it (EOF1 will) */
+   d->hdr1_seen = 0; }
 
 static const char *format_block_errors(struct rt_dec *d, struct rt_results *result, char *buf) {   /* src/readtape.c:1179-1209 */
    char *p = buf;
@@ -112,10 +115,65 @@ static void text_datablock(struct rt_dec *d, struct rt_results *result, int leng
    d->text_record(d->text, bytes, length, result->errcount, result->warncount, head);
    free(bytes); }
 
-void rt_got_datablock(struct rt_dec *d, int badblock) {   /* src/readtape.c:1212-1313 (no labels) */
+/* ---- IBM standard tape labels (src/ibmlabels.c:118-168): 80-byte blocks of EBCDIC text that start VOL1, HDR1/EOF1/EOV1 or HDR2/EOF2/EOV2.
+ * They are logged; without -tap they are not data (not written, not counted), HDR1 names the data file that follows
+ * <outbase>-NNN-<dataset id>.bin and EOF1 closes it.  The table is the label reader's own (unmapped codes are '?', src/ibmlabels.c:71-87),
+ * not the text dump's. ---- */
+static unsigned char label_ascii(uint16_t w) {
+   static const char rows4_7[4][17] = { " ?????????[.<(+|", "&?????????" "!$*);^", "-/????????|,%_>?", "?????????`:#|'=\"" };
+   const unsigned c = (w >> 1) & 0xff, hi = c >> 4, lo = c & 15;
+   if (c == 0x00 || c == 0xff) return ' ';
+   if (hi >= 4 && hi <= 7) return (unsigned char)rows4_7[hi - 4][lo];
+   if (hi >= 8 && hi <= 0xa) {                                  /* lower case: a-i, j-r, ~ s-z */
+      if (hi == 0xa) return lo == 1 ? '~' : (lo >= 2 && lo <= 9) ? (unsigned char)('s' + lo - 2) : '?';
+      return (lo >= 1 && lo <= 9) ? (unsigned char)((hi == 8 ? 'a' : 'j') + lo - 1) : '?'; }
+   if (hi >= 0xc && hi <= 0xe) {                                /* upper case, with { } \ in column 0 */
+      if (lo == 0) return (unsigned char)"{}\\"[hi - 0xc];
+      if (hi == 0xe) return (lo >= 2 && lo <= 9) ? (unsigned char)('S' + lo - 2) : '?';
+      return lo <= 9 ? (unsigned char)((hi == 0xc ? 'A' : 'J') + lo - 1) : '?'; }
+   if (hi == 0xf) return lo <= 9 ? (unsigned char)('0' + lo) : '?';
+   return '?'; }
+
+/* a field of the label as a string without its trailing blanks */
+static const char *label_field(const unsigned char *text, int at, int len, char *buf) {
+   memcpy(buf, text + at, (size_t)len);
+   while (len > 0 && buf[len - 1] == ' ') --len;
+   buf[len] = 0;
+   return buf; }
+
+static int absorb_label(struct rt_dec *d, const struct rt_results *result) {
+   if (result->minbits != 80) return 0;
+   unsigned char t[81];
+   for (int i = 0; i < 4; ++i) t[i] = label_ascii(d->data[i]);
+   const int seq = t[3] == '1' ? 1 : t[3] == '2' ? 2 : 0;
+   const int vol = !memcmp(t, "VOL", 3), hdr = !memcmp(t, "HDR", 3), eof = !memcmp(t, "EOF", 3), eov = !memcmp(t, "EOV", 3);
+   if (!seq || !(hdr || eof || eov || (vol && seq == 1))) return 0;
+   for (int i = 4; i < 80; ++i) t[i] = label_ascii(d->data[i]);
+   t[80] = 0;
+   char a[20], b[20], c[20];
+   if (vol) rlog(d, "*** tape label %.4s, serno \"%s\", owner \"%s\"\n", t, label_field(t, 4, 6, a), label_field(t, 41, 10, b));
+   else if (seq == 1) {
+      rlog(d, "*** tape label %.4s, dsid \"%s\", serno \"%s\", created%s\n", t, label_field(t, 4, 17, a), label_field(t, 21, 6, b), label_field(t, 41, 6, c));
+      rlog(d, "    volume %s, dataset %s\n", label_field(t, 27, 4, a), label_field(t, 31, 4, b));
+      if (eof) rlog(d, "    block count %.6s, system %s\n", t + 54, label_field(t, 60, 13, a)); }
+   else {
+      rlog(d, "*** tape label %.4s, RECFM=%.1s%.1s, BLKSIZE=%s, LRECL=%s\n", t, t + 4, t + 38, label_field(t, 5, 5, a), label_field(t, 10, 5, b));
+      rlog(d, "    job: \"%s\"\n", label_field(t, 17, 17, a)); }
+   if (result->errcount) rlog(d, "--> %d errors\n", result->errcount);
+   if (seq == 1 && hdr) {
+      if (!d->opt.tap_format && d->outbase[0]) {
+         char name[1080];
+         snprintf(name, sizeof name, "%.1024s-%03d-%s", d->outbase, d->numfiles + 1, label_field(t, 4, 17, a));
+         open_output(d, name); }
+      d->hdr1_seen = 1; }
+   if (seq == 1 && eof && !d->opt.tap_format && d->outbase[0]) rt_close_output(d);
+   return 1; }
+
+void rt_got_datablock(struct rt_dec *d, int badblock) {   /* src/readtape.c:1212-1313 */
    struct rt_results *result = &d->results[d->parmset];
    int length = result->minbits;
-   if (length > 0) {
+   const int labelled = !badblock && d->labels && absorb_label(d, result);
+   if (length > 0 && (d->opt.tap_format || !labelled)) {
       if (badblock) {
          ++d->numblks_unusable;
          rlog(d, "ERROR: unusable block, ");
@@ -125,7 +183,7 @@ void rt_got_datablock(struct rt_dec *d, int badblock) {   /* src/readtape.c:1212
       else {
          uint32_t errflag = result->errcount ? 0x80000000u : 0;
          d->last_block_time = d->timenow;
-         if (!d->tapf) open_output(d);
+         if (!d->tapf) open_output(d, NULL);
          if (d->opt.tap_format) output_tap_marker(d, (uint32_t)length | errflag);
          for (int i = 0; i < length; ++i) {
             unsigned char b = (unsigned char)(d->data[i] >> 1);
@@ -220,8 +278,20 @@ static int best_attempt(const struct rt_dec *d, int *tier_out) {
    *tier_out = best_tier;
    return best; }
 
+static __thread struct { int set, labels, blklimit; } g_run_request;
+void rt_driver_set_run(int labels, int blklimit) {
+   g_run_request.set = 1; g_run_request.labels = labels; g_run_request.blklimit = blklimit; }
+
+static void end_of_blocks(struct rt_dec *d, int blklimit) {      /* src/readtape.c:1884-1887 */
+   if (d->numblks >= blklimit) rlog(d, "\n***blklimit=%d reached\n", blklimit);
+   rt_tap_end(d); }
+
 int rt_process_blocks(struct rt_dec *d, struct rt_reader *r, int blklimit) {
    int all_clean = 1, out_of_data = 0;
+   if (g_run_request.set) {
+      g_run_request.set = 0;
+      d->labels = g_run_request.labels;
+      if (g_run_request.blklimit >= 0 && g_run_request.blklimit < blklimit) blklimit = g_run_request.blklimit; }
    const int ww = d->opt.mode == RT_WW;
    d->interblock_counter = 0;
    if (ww && !d->ww_prepassed) rt_init_trackstate(d);             /* Whirlwind: once per tape - blocks may be one bit apart (src/readtape.c:1674); a -deskew pre-pass has done it */
@@ -240,7 +310,7 @@ int rt_process_blocks(struct rt_dec *d, struct rt_reader *r, int blklimit) {
          else out_of_data = !r->readblock(r->ctx, d->tries > 0);
          if (d->fatal) return 0;                                  /* the reference has exited (src/decoder.c:709-710,748,782): no other parameter set is tried */
          const struct rt_results *a = &d->results[d->parmset];
-         if (a->blktype == RT_BS_NONE) { rt_tap_end(d); return all_clean; }      /* what was left of the data was no block */
+         if (a->blktype == RT_BS_NONE) { end_of_blocks(d, blklimit); return all_clean; }      /* what was left of the data was no block */
          ++d->tries;
          ++RT_PARM(d).tried;
          if (attempt_is_final(a)) {
@@ -274,7 +344,7 @@ int rt_process_blocks(struct rt_dec *d, struct rt_reader *r, int blklimit) {
       case RT_BS_BLOCK:    rt_got_datablock(d, 0); break;
       case RT_BS_BADBLOCK: rt_got_datablock(d, 1); break;
       default: return 0; } }
-   rt_tap_end(d);
+   end_of_blocks(d, blklimit);
    return all_clean; }
 
 /* ---- -deskew pre-pass (src/readtape.c:1675-1717 + skew_compute_deskew / skew_set_delay, src/decoder.c:235-281) ---- */

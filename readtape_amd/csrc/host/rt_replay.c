@@ -571,7 +571,7 @@ static int pred_ww(const struct rt_dec *d, const struct rt_trk *t, double timeno
    (void)t;
    return timenow - d->ww.t_lastclkpulseend > d->ww.clkavg.t_bitspaceavg * 1.5f; }             /* WW_CLKSTOP_BITS */
 
-static int ww_readblock(void *ctx, int retry) {
+static int ww_readblock_once(void *ctx, int retry) {
    struct rt_replay *rp = (struct rt_replay *)ctx;
    struct rt_dec *d = rp->d;
    const int ntrks = rp->ntrks, W = rp->W[0];
@@ -645,6 +645,13 @@ static int ww_readblock(void *ctx, int retry) {
          ++rp->device_failures; d->results[d->parmset].blktype = RT_BS_ABORTED; rt_finish_attempt(d); return 0; } }
    rt_finish_attempt(d);
    return !endfile; }
+
+static int ww_readblock(void *ctx, int retry) {             /* the summary's "samples": as rt_replay_readblock counts them */
+   struct rt_replay *rp = (struct rt_replay *)ctx;
+   const int64_t from = rp->pos;
+   const int more = ww_readblock_once(ctx, retry);
+   if (!retry) rp->d->lines_in += (rp->pos - from) + (more ? 0 : 1);
+   return more; }
 
 int rt_replay_run_ww(const struct rt_options *opt, const struct rt_parms *parmsets,
                   int64_t tdelta_ns, int64_t tstart_ns, int64_t nrows, int W0, rt_ww_scan_fn scan, void *user, const void *initial_state, int64_t chunk_rows,

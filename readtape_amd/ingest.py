@@ -393,7 +393,7 @@ def decode_file_streaming(path, tap_path, window_rows=1 << 24, halo_rows=1 << 17
         mark("replay", k, t0)
         return out
 
-    stats = dict(rows=nrows, windows=len(spans), halo_rows_read=0, blocks=0, tapemarks=0, events_delivered=0, exact_scans=0, retries=0, replay_threads=nthreads)
+    stats = dict(rows=nrows, windows=len(spans), halo_rows_read=0, blocks=0, tapemarks=0, events_delivered=0, exact_scans=0, retries=0, replay_threads=nthreads, all_ok=True)
     t_replay = 0.0
     for f in fes:                                         # set-up, like the pinned buffers and the device windows: the scan contexts' workspaces
         f._pack_buffers(f._buffers(cap), f._buffers(cap)["cap"] // 2)
@@ -539,6 +539,7 @@ def decode_file_streaming(path, tap_path, window_rows=1 << 24, halo_rows=1 << 17
                     total += len(data)
                     for key in ("blocks", "tapemarks", "events_delivered", "exact_scans"):
                         stats[key] += int(st[key])
+                    stats["all_ok"] = bool(stats["all_ok"] and st["all_ok"])      # (every fragment's blocks were clean: the reference's "ok")
             if total > 0:
                 tapf.write(b"\xff\xff\xff\xff")                   # src/readtape.c:1885
         torch.cuda.synchronize(dev)

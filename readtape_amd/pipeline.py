@@ -259,21 +259,29 @@ def decode_tape(hdr, rows, tap_path, log_path=None, opts: DecodeOptions | None =
                 skew=None, invert=False, parms_text: str | None = None, find_zeros=False, evt_path=None, differentiate=False,
                 subsample: int = 1, deskew: bool = False, deskew_prefix_rows: int = 1 << 22, trkorder: str | None = None,
                 out_base: str | None = None, in_name: str | None = None, tap_format: bool = True, fluxdir: str = "neg", reverse: bool = False,
-                textfile=None, created=None):
+                textfile=None, created=None, labels: bool = False, blklimit: int | None = None, skip: int = 0):
     """Decodes one tape; returns (stats dict, ScanResult).  `fe_factory(cfg)` builds the front end
     (default: the GPU one; tests/cpu_emul passes the emulated library).
     Output: tap_path = one SIMH .tap file; or out_base = the reference's own naming - <out_base>.tap, or with tap_format=False
     the numbered <out_base>.NNN.bin data files, one per tape file (src/readtape.c:1091-1111) - with the files' creation/closing
     and the end-of-run summary (src/readtape.c:2021-2044; in_name = the input's name in it) in the log.
     textfile = textfile.TextOptions(...): the reference's -textfile - the interpreted text of every block, in the verbose layout, in
-    textfile.text_name(out_base or tap_path without its extension, textfile); created: the date in its title (textfile.write_text)."""
+    textfile.text_name(out_base or tap_path without its extension, textfile); created: the date in its title (textfile.write_text).
+    labels: IBM standard labels (VOL1, HDR1/2, EOF1/2, EOV1/2; src/ibmlabels.c) are logged and, without tap_format, absorbed, the data files
+    named <out_base>-NNN-<dsid>.bin - the reference's default, its -nolabels is labels=False.  blklimit: the reference's -blklimit=n, the
+    decode stops once n blocks are written.  skip: the reference's -skip=n - the first n raw rows are not part of the tape (before
+    -subsample; the time base starts at the header's tstart on the first row used, as in ingest.decode_file_streaming)."""
     opts = opts or DecodeOptions()
+    if skip:
+        if skip < 0 or skip > int(rows.shape[0]):                          # "endfile with %d lines left to skip" (src/readtape.c:1641)
+            raise ReferenceFatal(f"the input ends with {skip - int(rows.shape[0])} rows left to skip", {"reference_fatal": 1, "events_delivered": 0})
+        rows = rows[skip:]
     if opts.add_parity and hdr.ntrks >= 9:
         raise ValueError(f"-addparity is not allowed with ntrks={hdr.ntrks}")      # src/readtape.c:1645
     if hdr.mode == tbin.MODE_WW:                                           # one chain per tape, detector state handed back and forth: its own path
         st = decode_tape_ww(hdr, rows, tap_path, log_path=log_path, order=trkorder, verbose=opts.verbose, evt_path=evt_path, fe_factory=fe_factory,
                             invert=invert, out_base=out_base, in_name=in_name, deskew=deskew, fluxdir=fluxdir, reverse=reverse,      # (-fluxdir, -reverse: Whirlwind only)
-                            find_zeros=find_zeros, differentiate=differentiate, textfile=textfile, created=created)
+                            find_zeros=find_zeros, differentiate=differentiate, textfile=textfile, created=created, labels=labels, blklimit=blklimit)
         return st, None
     lib = _load_decode_lib()
     if trkorder:                                                           # -order= wins over the header's TBINORD extension (src/readtape.c:1346-1355)
@@ -327,6 +335,7 @@ def decode_tape(hdr, rows, tap_path, log_path=None, opts: DecodeOptions | None =
     exact, free, keep = _exact_callbacks(fe, rows, hdr.ntrks, fe_factory)
 
     _request_text(lib, textfile, out_base, tap_path, created)
+    _request_run(lib, labels, blklimit)
     st = _Stats()
     bursts = np.ascontiguousarray(res.bursts)
     counts = np.ascontiguousarray(res.counts)
@@ -343,6 +352,7 @@ def decode_tape(hdr, rows, tap_path, log_path=None, opts: DecodeOptions | None =
                  exact, free, None,
                  tap_path.encode() if tap_path else None, log_path.encode() if log_path else None,
                  evt_path.encode() if evt_path else None, C.byref(st))
+    lib.rt_driver_set_run(0, -1)                                          # (a run that never reached its blocks leaves nothing behind for the next)
     _release(keep)
     if rc != 0:
         raise RuntimeError("rt_replay_run failed")
@@ -375,9 +385,17 @@ def _request_text(lib, opts, out_base, tap_path, created):
     lib.rt_replay_set_text(C.byref(o), os.fsencode(base), tf._created(created))
 
 
+def _request_run(lib, labels, blklimit):
+    """labels= and blklimit= for the decode that is about to start on this thread (rt_driver_set_run)."""
+    if blklimit is not None and blklimit < 0:
+        raise ValueError("blklimit must not be negative")
+    lib.rt_driver_set_run.argtypes = [C.c_int, C.c_int]
+    lib.rt_driver_set_run(int(bool(labels)), -1 if blklimit is None else min(int(blklimit), 0x7fffffff))
+
+
 def decode_tape_ww(hdr, rows, tap_path, log_path=None, order: str | None = None, fluxdir: str = "neg", reverse: bool = False, verbose: bool = True,
                    evt_path=None, fe_factory=None, invert=False, chunk_rows: int = 4096, out_base=None, in_name=None, deskew: bool = False,
-                   find_zeros: bool = False, differentiate: bool = False, textfile=None, created=None):
+                   find_zeros: bool = False, differentiate: bool = False, textfile=None, created=None, labels: bool = False, blklimit: int | None = None):
     """Decodes a Whirlwind tape (6 tracks, 100 BPI; mode WW in the header or by the caller).  order = the heads' roles (-order=CMLcml,
     default: the header's TBINORD string); fluxdir neg / pos / auto.  The device detector keeps its state across block attempts, so
     the host replay fetches its events in chunks and hands the state back in (rtfe_ww_scan).  deskew: the reference's
@@ -429,6 +447,7 @@ def decode_tape_ww(hdr, rows, tap_path, log_path=None, order: str | None = None,
 
     cb = _WW_SCAN_FN(scan)
     _request_text(lib, textfile, out_base, tap_path, created)
+    _request_run(lib, labels, blklimit)
     st = _Stats()
     init = fe.ww_initial_state()
     delays = (C.c_int * hdr.ntrks)()
@@ -436,6 +455,7 @@ def decode_tape_ww(hdr, rows, tap_path, log_path=None, order: str | None = None,
                               tap_path.encode() if tap_path and not out_base else None, out_base.encode() if out_base else None,
                               (in_name or "").encode() if (out_base and in_name) else None, log_path.encode() if log_path else None,
                               evt_path.encode() if evt_path else None, C.byref(st), int(bool(deskew)), delays)
+    lib.rt_driver_set_run(0, -1)
     fe.close()
     if rc == -2 and not bad:
         raise RuntimeError("the -deskew pre-pass found tracks without flux transitions (is the order string right?)")
