@@ -95,10 +95,16 @@ options:
                  file of the list, otherwise each file's own name follows -outp=
   --stream       decode a .tbin through device windows instead of reading it whole
                  (needs -tap and -nolabels; not for Whirlwind, -textfile or -blklimit; no log)
+  --peakstats    write <basefilename>.peakstats.csv (and, with -deskew, .peakstats_deskew.csv):
+                 per track, where the flux transitions fall against the decoder's clock; and
+                 say under the summary whether the head skew is significant (-q: only the
+                 -deskew file, as in readtape; every file of a -f list gets its own; not with
+                 --stream, whose windows do not share the bins the first transition fixes)
 
 not built (the run ends with status 2): -showibg=n -sumt=sss -sumc=ccc -adjskew -d[n]
-  <basefilename>.peakstats.csv is not written: gathering it would put a histogram update
-  on every flux transition of the host replay, which bounds the end-to-end rate.
+  <basefilename>.peakstats.csv is not written unless --peakstats is given: gathering it puts
+  a histogram update on every flux transition of every attempt of the host replay, which
+  then takes 1.05 times as long (an NRZI tape, one parameter set; profiles/peakstats.txt).
 """
 
 
@@ -159,6 +165,7 @@ class Options:
     multiple_tries: bool = True
     filelist: bool = False
     stream: bool = False
+    peakstats: bool = False
 
     def text_options(self):
         """-textfile's options as the run uses them (src/readtape.c:1940-1946): any number or character type asks for the file; 32 characters a line
@@ -307,8 +314,11 @@ def parse_option(o: Options, option: str) -> bool:
         return False
     arg = option[1:]
     up = arg.upper()
-    if up == "-STREAM":                                       # (ours, not the reference's: the one long option)
+    if up == "-STREAM":                                       # (ours, not the reference's: the long options)
         o.stream = True
+        return True
+    if up == "-PEAKSTATS":
+        o.peakstats = True
         return True
     ok, n = _int(arg, "NTRKS=", MINTRKS, MAXTRKS)
     if ok:
@@ -529,6 +539,8 @@ def decode_file(o: Options, name, fe_factory, out, outbase_of):
     text_opts = o.text_options()
     if o.stream:
         why = "--stream reads a .tbin file" if kind != "tbin" else _stream_refusal(o, mode)
+        if o.peakstats:
+            why = "--stream gathers no flux-transition statistics: leave --peakstats out (its bins are fixed by the tape's first transition, which only the first window sees)"
         if why:
             raise CliExit(2, why + "\n")
     if kind == "csv":
@@ -575,7 +587,8 @@ def decode_file(o: Options, name, fe_factory, out, outbase_of):
             stats, _ = pipeline.decode_tape(hdr, rows, None, log_path=log_path, opts=_decode_options(o), fe_factory=fe_factory, skew=o.skew, invert=o.invert,
                                             parms_text=parms_text, find_zeros=o.find_zeros, differentiate=o.differentiate, subsample=o.subsample,
                                             deskew=o.deskew, trkorder=o.order or None, out_base=out_base, in_name=path, tap_format=o.tap_format,
-                                            fluxdir=o.fluxdir, reverse=o.reverse, textfile=text_opts, labels=o.labels, blklimit=o.blklimit, skip=o.skip)
+                                            fluxdir=o.fluxdir, reverse=o.reverse, textfile=text_opts, labels=o.labels, blklimit=o.blklimit, skip=o.skip,
+                                            peakstats=o.peakstats, quiet=o.quiet)
         finally:
             if log_path and not o.quiet and os.path.exists(log_path):
                 with open(log_path, errors="replace") as f:

@@ -182,9 +182,14 @@ struct rt_dec {
    int     numblks, numtapemarks, numblks_err, numblks_warn, numblks_unusable;
    int     numblks_goodmultiple, numblks_trksmismatched, numblks_midbiterrs, numblks_corrected;
    FILE   *logf;                    /* block log lines (NULL = quiet) */
-   /* flux-transition position statistics of the -deskew pre-pass (src/decoder.c:121-173): only gathered while
-    * doing_deskew (in the reference they also feed a .csv report, which is out of scope) */
+   /* flux-transition position statistics (src/decoder.c:121-173): gathered while doing_deskew (the -deskew pre-pass), and in
+    * the decode itself when want_peakstats asks for the reference's <base>.peakstats.csv report and its head-skew verdict
+    * (rt_peakstats_report; peak_base names the files, peak_quiet is the reference's -q, peak_deskew its `deskew` flag) */
    int     doing_deskew;
+   int     want_peakstats, peak_quiet, peak_deskew;
+   char    peak_base[1024];
+   float   deskew_max_delay_percent;                            /* src/decoder.c:233,280: what the pre-pass set the delays to */
+   struct { int ok; float peak_frac, stddev_frac; } skew_verdict;   /* the last rt_skew_verdict */
    /* density detection (src/decoder.c:329-394, src/readtape.c:1656-1672): while bpi is unknown every transition goes
     * to a histogram of transition distances instead of a block decoder */
    int     doing_density_detection;
@@ -286,6 +291,13 @@ void rt_driver_set_run(int labels, int blklimit);
  * Returns the number of blocks used (>= 0), or -1 if some track saw no transition; *hit_end = 1 if the reader ran out
  * of data before the reference's stopping rule was met (the caller may then retry on a longer prefix of the tape). */
 void rt_record_peakstat(struct rt_dec *d, float bitspacing, float peaktime, int trknum);   /* src/decoder.c:136-173 */
+#define RT_RECORDING_PEAKSTATS(d) ((d)->doing_deskew | (d)->want_peakstats)                /* the one test a decoder's record site costs */
+/* the report on them (want_peakstats): <peak_base>.peakstats<suffix>.csv (output_peakstats, src/decoder.c:175-214; returns 0 if it
+ * could not be made), the two lines of numbers of skew_compute_deskew (src/decoder.c:243-281; returns its verdict and leaves it in
+ * d->skew_verdict), and what the reference puts under its summary (src/readtape.c:2045-2058): file, numbers, one of four sentences */
+int  rt_output_peakstats(struct rt_dec *d, const char *suffix);
+int  rt_skew_verdict(struct rt_dec *d);
+void rt_peakstats_report(struct rt_dec *d);
 
 /* ---- density detection (src/readtape.c:1656-1672): reads attempts with bpi = 0 until RT_ESTDEN_COUNTNEEDED transition
  * distances are in the histogram (or the data ends), then picks the standard density.  Returns the density (d->opt.bpi

@@ -82,7 +82,7 @@ static void zeros_before(struct rt_dec *d, struct rt_trk *t, float gap) {
 static void transition(struct rt_dec *d, struct rt_trk *t, int is_top) {
    const double when = is_top ? t->t_top : t->t_bot;
    const float gap = (float)(when - t->t_lastpeak);
-   if (d->doing_deskew && t->t_lastclock != 0) rt_record_peakstat(d, t->clkavg.t_bitspaceavg, gap, t->trknum);
+   if (RT_RECORDING_PEAKSTATS(d) && t->t_lastclock != 0) rt_record_peakstat(d, t->clkavg.t_bitspaceavg, gap, t->trknum);
    zeros_before(d, t, gap);
    put_bit(d, t, 1, when);
    const int settled = t->peakcount > AGC_ENDBASE;

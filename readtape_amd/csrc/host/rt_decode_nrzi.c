@@ -130,7 +130,7 @@ static void transition(struct rt_dec *d, struct rt_trk *t, int is_top) {
    struct rt_nrzi *z = &d->nrzi;
    const double when = is_top ? t->t_top : t->t_bot;
    const int in_data = z->post_counter == 0;
-   if (d->doing_deskew && in_data && z->datablock && z->t_lastclock != 0)
+   if (RT_RECORDING_PEAKSTATS(d) && in_data && z->datablock && z->t_lastclock != 0)      /* src/decode_nrzi.c:187,202 */
       rt_record_peakstat(d, z->clkavg.t_bitspaceavg, (float)(when - z->t_lastclock), t->trknum);
    if (in_data && when < z->t_last_midbit) ++d->results[d->parmset].missed_midbits;
    put_bit(d, t, 1, when);

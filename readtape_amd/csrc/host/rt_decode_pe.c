@@ -116,6 +116,7 @@ static void preamble_transition(struct rt_dec *d, struct rt_trk *t, int is_top, 
 static void transition(struct rt_dec *d, struct rt_trk *t, int is_top) {   /* src/decode_pe.c:157-201 */
    const double when = is_top ? t->t_top : t->t_bot;
    if (!t->datablock) { preamble_transition(d, t, is_top, when); return; }
+   if (RT_RECORDING_PEAKSTATS(d)) rt_record_peakstat(d, t->clkavg.t_bitspaceavg, (float)(when - t->t_lastpeak), t->trknum);   /* src/decode_pe.c:160,183 */
    /* more than a clock window after the previous transition (the last pulse's shift taken out): the cell-boundary
     * transition is missing, so this one carries data whatever was expected */
    const int boundary_missing = (when + t->t_pulse_adj) - t->t_lastpeak > t->t_clkwindow;

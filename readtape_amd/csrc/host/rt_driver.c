@@ -6,6 +6,7 @@
 
 #include <float.h>
 #include <limits.h>
+#include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -347,6 +348,81 @@ int rt_process_blocks(struct rt_dec *d, struct rt_reader *r, int blklimit) {
    end_of_blocks(d, blklimit);
    return all_clean; }
 
+/* ---- the flux-transition statistics' report: <base>.peakstats[_deskew].csv and the head-skew verdict ---- */
+#define DESKEW_PEAKDIFF_WARNING 0.20      /* src/decoder.h:44-45: fractions of a bit (double literals, as there) */
+#define DESKEW_STDDEV_WARNING   0.05
+
+int rt_output_peakstats(struct rt_dec *d, const char *suffix) {   /* src/decoder.c:175-214 */
+   const int B = RT_PEAKSTAT_BUCKETS;
+   const float left = d->peakstat.leftbin, bw = d->peakstat.binwidth;
+   char filename[1100], cb[32];
+   int totalcount = 0;
+   snprintf(filename, sizeof filename, "%s.peakstats%s.csv", d->peak_base, suffix);
+   FILE *f = fopen(filename, "w");
+   if (!f) return 0;
+   fprintf(f, "total cnt, <=%.1f uS, >=%.1f uS, track", left * 1e6, bw * 1e6 * (B - 1) + left * 1e6);
+   for (int b = 1; b < B - 1; ++b) fprintf(f, ",%.1f uS", bw * 1e6 * b + left * 1e6);
+   if (d->opt.mode == RT_NRZI) fprintf(f, ",avg uS");
+   fprintf(f, "\n");
+   for (int t = 0; t < d->opt.ntrks; ++t) {
+      const int *c = d->peakstat.counts[t], sum = d->peakstat.trksums[t];
+      long long avgsum = 0;                                     /* (the two catch-all buckets do not count) */
+      for (int b = 1; b < B - 1; ++b) avgsum += (long long)(c[b] * (bw * 1e6 * b + left * 1e6));
+      fprintf(f, "%d, %d, %d,", sum + c[0] + c[B - 1], c[0], c[B - 1]);
+      fprintf(f, "trk%d", t);
+      for (int b = 1; b < B - 1; ++b) fprintf(f, ", %.2f%%", sum ? 100 * (float)c[b] / (float)sum : 0);
+      if (d->opt.mode == RT_NRZI) fprintf(f, ", %.2f", (float)avgsum / (float)sum);      /* (0 / 0 as the C library prints it) */
+      fprintf(f, "\n");
+      totalcount += sum; }
+   fclose(f);
+   if (!d->peak_quiet) {
+      rlog(d, "  created statistics file \"%s\" from %s measurements of flux transition positions\n", filename, commas(totalcount, cb));
+      rlog(d, "  to graph it from Excel, open the CSV file, then: insert chart 2D line\n"); }
+   d->peakstat.initialized = 0;
+   return 1; }
+
+int rt_skew_verdict(struct rt_dec *d) {   /* skew_compute_deskew's numbers and its answer (src/decoder.c:243-281) */
+   const int B = RT_PEAKSTAT_BUCKETS, ntrks = d->opt.ntrks;
+   const float left = d->peakstat.leftbin, bw = d->peakstat.binwidth;
+   float avg[RT_MAXTRKS], stddev[RT_MAXTRKS];
+   for (int t = 0; t < ntrks; ++t) {
+      long long avgsum = 0;
+      for (int b = 1; b < B - 1; ++b) avgsum += (long long)(d->peakstat.counts[t][b] * (bw * 1e6 * b + left * 1e6));
+      avg[t] = (float)avgsum / (float)d->peakstat.trksums[t]; }
+   for (int t = 0; t < ntrks; ++t) {
+      stddev[t] = 0;
+      for (int b = 1; b < B - 1; ++b) {
+         const float deviation = (bw * 1e6f * b + left * 1e6f) - avg[t];
+         stddev[t] += d->peakstat.counts[t][b] * (deviation * deviation); }
+      stddev[t] = sqrtf(stddev[t] / (float)d->peakstat.trksums[t]); }
+   float maxavg = 0, minavg = FLT_MAX, maxstddev = 0;
+   for (int t = 0; t < ntrks; ++t) {                            /* (the reference's max / min macros, operands in its order: a NaN average is taken) */
+      maxavg = maxavg > avg[t] ? maxavg : avg[t];
+      minavg = minavg < avg[t] ? minavg : avg[t];
+      maxstddev = maxstddev > stddev[t] ? maxstddev : stddev[t]; }
+   const float peak_frac = (maxavg - minavg) / (1e6f / (d->opt.bpi * d->opt.ips));
+   const float stddev_frac = maxstddev / (1e6f / (d->opt.bpi * d->opt.ips));
+   if (!d->peak_quiet) {
+      rlog(d, "  the earliest peak is %.2f usec, and the latest peak is %.2f usec\n", minavg, maxavg);
+      rlog(d, "  that peak difference of %.2f usec, and the largest standard deviation of %.2f usec, are %.1f%% and %.1f%% of the nominal bit spacing\n",
+           maxavg - minavg, maxstddev, peak_frac * 100, stddev_frac * 100); }
+   d->skew_verdict.peak_frac = peak_frac; d->skew_verdict.stddev_frac = stddev_frac;
+   d->skew_verdict.ok = peak_frac < DESKEW_PEAKDIFF_WARNING && stddev_frac < DESKEW_STDDEV_WARNING;
+   return d->skew_verdict.ok; }
+
+void rt_peakstats_report(struct rt_dec *d) {   /* src/readtape.c:2045-2058; with -q the reference reports nothing here */
+   if (d->peak_quiet) { rt_skew_verdict(d); return; }           /* (the caller may still want the numbers) */
+   rlog(d, "\n");
+   rt_output_peakstats(d, "");
+   if (rt_skew_verdict(d)) {
+      if (d->peak_deskew) rlog(d, "  deskewing with delays up to %.1f%% of a bit time seems to have been successful\n", d->deskew_max_delay_percent);
+      else rlog(d, "  the tape data head skew is minimal\n"); }
+   else {
+      if (d->peak_deskew) rlog(d, "  deskewing with delays up to %.1f%% of a bit time wasn't entirely effective\n"
+                                  "  the tape might have been written by two different drives\n"
+                                  "  if so you should consider separating the data into those sections\n", d->deskew_max_delay_percent);
+      else rlog(d, "  head skew is significant; you should try again with the -deskew option\n"); } }
+
 /* ---- -deskew pre-pass (src/readtape.c:1675-1717 + skew_compute_deskew / skew_set_delay, src/decoder.c:235-281) ---- */
 int rt_deskew_prepass(struct rt_dec *d, struct rt_reader *r, int delays[RT_MAXTRKS], int *hit_end) {
    const int ntrks = d->opt.ntrks;
@@ -387,6 +463,10 @@ int rt_deskew_prepass(struct rt_dec *d, struct rt_reader *r, int delays[RT_MAXTR
       delays[t] = delay < RT_MAXSKEWSAMP ? delay : RT_MAXSKEWSAMP;
       rlog(d, "  track %d delayed by %d clocks (%.2f usec) based on %d observed flux transitions\n",
            t, delays[t], delays[t] * d->sample_deltat * 1e6, d->peakstat.trksums[t]); }
+   if (d->want_peakstats) {                                  /* the rest of skew_compute_deskew(true), then output_peakstats("_deskew") (src/readtape.c:1701-1704) */
+      rt_skew_verdict(d);
+      d->deskew_max_delay_percent = d->skew_verdict.peak_frac * 100;
+      rt_output_peakstats(d, "_deskew"); }
    d->peakstat.initialized = 0;
    if (ww) {                                                 /* the pulse heights learned on the way (src/readtape.c:1706-1716); the caller resets the detector */
       rlog(d, "\n");

@@ -210,7 +210,7 @@ static int readblock_once(void *ctx, int retry) {
    /* ... and what a pre-pass accumulates ACROSS attempts (the -deskew peak statistics, the density histogram): the reference reads
     * the block once, a restarted attempt must not count its transitions twice (found by tests/stress_gpu.py, seed 810 tape 100:
     * the pre-pass had its 1000 transitions per track one block early) */
-   const int prepass_stats = d->doing_deskew || d->doing_density_detection;
+   const int prepass_stats = d->doing_deskew || d->doing_density_detection || d->want_peakstats;      /* (... and what --peakstats gathers across the whole decode) */
    __typeof__(d->peakstat) saved_peakstat; __typeof__(d->estden) saved_estden;
    if (prepass_stats) { saved_peakstat = d->peakstat; saved_estden = d->estden; }
    int64_t b = find_burst(rp, s0);
@@ -380,6 +380,41 @@ static struct rt_textfile *text_attach(struct rt_dec *d) {
    d->text = t; d->text_name = rt_text_filename(t); d->text_record = text_record_hook; d->text_tapemark = text_tapemark_hook;
    return t; }
 
+/* ---- the flux-transition statistics of the next decode (<base>.peakstats.csv, <base>.peakstats_deskew.csv and the head-skew verdict): asked for by
+ * rt_replay_set_peakstats on the calling thread.  A -deskew pre-pass on this thread reads the request and leaves what it learned (the largest delay as
+ * a percentage of a bit, its histogram) with it; the run that processes blocks takes it.  Fragments never do: the bins are fixed by the tape's first
+ * recorded transition, which only the first fragment sees. ---- */
+struct peak_result { int valid, ok; float peak_frac, stddev_frac, leftbin, binwidth; int counts[RT_MAXTRKS][RT_PEAKSTAT_BUCKETS], trksums[RT_MAXTRKS]; };
+static __thread struct { int set, quiet, deskew; char base[1024]; float deskew_pct; struct peak_result res[2]; } g_peak_request;
+void rt_replay_set_peakstats(const char *base, int quiet, int deskew) {
+   memset(&g_peak_request, 0, sizeof g_peak_request);
+   if (!base) return;
+   snprintf(g_peak_request.base, sizeof g_peak_request.base, "%s", base);
+   g_peak_request.quiet = quiet; g_peak_request.deskew = deskew;
+   g_peak_request.set = 1; }
+int rt_replay_get_peakstats(int which, float *leftbin, float *binwidth, int32_t *counts, int32_t *trksums, int *ok, float *peak_frac, float *stddev_frac) {
+   if (which < 0 || which > 1 || !g_peak_request.res[which].valid) return 0;
+   const struct peak_result *r = &g_peak_request.res[which];
+   *leftbin = r->leftbin; *binwidth = r->binwidth; *ok = r->ok; *peak_frac = r->peak_frac; *stddev_frac = r->stddev_frac;
+   memcpy(counts, r->counts, sizeof r->counts); memcpy(trksums, r->trksums, sizeof r->trksums);
+   return 1; }
+static int peak_attach(struct rt_dec *d) {                       /* both passes: the decoders record, the files are named */
+   if (!g_peak_request.set) return 0;
+   d->want_peakstats = 1; d->peak_quiet = g_peak_request.quiet; d->peak_deskew = g_peak_request.deskew;
+   snprintf(d->peak_base, sizeof d->peak_base, "%s", g_peak_request.base);
+   d->deskew_max_delay_percent = g_peak_request.deskew_pct;
+   return 1; }
+static void peak_keep(struct rt_dec *d, int which) {
+   struct peak_result *r = &g_peak_request.res[which];
+   r->valid = 1; r->ok = d->skew_verdict.ok; r->peak_frac = d->skew_verdict.peak_frac; r->stddev_frac = d->skew_verdict.stddev_frac;
+   r->leftbin = d->peakstat.leftbin; r->binwidth = d->peakstat.binwidth;
+   memcpy(r->counts, d->peakstat.counts, sizeof r->counts); memcpy(r->trksums, d->peakstat.trksums, sizeof r->trksums);
+   g_peak_request.deskew_pct = d->deskew_max_delay_percent; }
+static void peak_report(struct rt_dec *d) {                      /* under the summary (src/readtape.c:2045-2058); the request is used up */
+   rt_peakstats_report(d);
+   peak_keep(d, 0);
+   g_peak_request.set = 0; }
+
 /* prepass != NULL: run the -deskew pre-pass instead of the decode (no .tap); append: keep what is already in the log
  * and event-dump files (the decode that follows a pre-pass continues both, as the reference's single run does) */
 struct deskew_out { int *delays; int *nblks; int *hit_end; float *bpi, *implied; };
@@ -417,13 +452,19 @@ static int replay_any(const struct rt_options *opt, const struct rt_parms *parms
       if (rp.evtf) { d->on_transition = dump_transition; d->on_attempt = dump_attempt; d->user = &rp; } }
    struct rt_reader rd = { rt_replay_readblock, rt_replay_save_pos, rt_replay_restore_pos, &rp };
    int ok = 1;
+   int peaks = 0;
    if (prepass && prepass->bpi) *prepass->bpi = rt_density_prepass(d, &rd, prepass->implied, prepass->nblks, prepass->hit_end);
-   else if (prepass) *prepass->nblks = rt_deskew_prepass(d, &rd, prepass->delays, prepass->hit_end);
+   else if (prepass) {
+      peaks = peak_attach(d);
+      *prepass->nblks = rt_deskew_prepass(d, &rd, prepass->delays, prepass->hit_end);
+      if (peaks && *prepass->nblks >= 0) peak_keep(d, 1); }
    else {
+      if (!fragment) peaks = peak_attach(d);
       struct rt_textfile *text = text_attach(d);
       ok = rt_process_blocks(d, &rd, 0x7fffffff);
       if (text) { d->text = NULL; d->text_record = NULL; d->text_tapemark = NULL; rt_text_close(text, 1); } }      /* src/readtape.c:1886 */
    if (in_name && !prepass) rt_write_summary(d, in_name, difftime(time(NULL), (time_t)wall0));
+   if (peaks && !prepass) peak_report(d);
    if (stats) {
       stats->attempts = rp.attempts; stats->exact_scans = rp.exact_scans; stats->chained = rp.chained;
       stats->events_delivered = rp.events_delivered; stats->agc_mismatches = rp.agc_mismatches;
@@ -713,6 +754,7 @@ int rt_replay_run_ww_detector(const struct rt_options *opt, const struct rt_parm
    const double wall0 = (double)time(NULL);
    struct rt_reader rd = { ww_readblock, rt_replay_save_pos, rt_replay_restore_pos, &rp };
    int prepass_failed = 0;
+   const int peaks = peak_attach(d);
    if (deskew) {
       /* -deskew (src/readtape.c:1676-1716): the first blocks are read once to learn the heads' skew and the pulse heights; then the
        * windows and the delay lines are cleared (init_trackpeak_state) - NOT the rings, the AGC or the decoder's track state -
@@ -723,12 +765,14 @@ int rt_replay_run_ww_detector(const struct rt_options *opt, const struct rt_parm
       rt_replay_restore_pos(&rp);
       if (nblks < 0 || rp.device_failures || rp.reference_fatal) prepass_failed = 1;
       else {
+         if (peaks) { peak_keep(d, 1); memset(&d->peakstat, 0, sizeof d->peakstat); }      /* (a decode that records nothing reports nothing: no stale counts) */
          ww_rewind_state(rp.ww_state, wide, o.ntrks, d, delays);
          if (delays_out) memcpy(delays_out, delays, sizeof(int) * (size_t)o.ntrks); } }
    struct rt_textfile *text = prepass_failed ? NULL : text_attach(d);
    const int ok = prepass_failed ? 0 : rt_process_blocks(d, &rd, 0x7fffffff);
    if (text) { d->text = NULL; d->text_record = NULL; d->text_tapemark = NULL; rt_text_close(text, 1); }
    if (in_name) rt_write_summary(d, in_name, difftime(time(NULL), (time_t)wall0));
+   if (peaks && !prepass_failed) peak_report(d);
    if (stats) {
       memset(stats, 0, sizeof *stats);
       stats->attempts = rp.attempts; stats->exact_scans = rp.exact_scans; stats->events_delivered = rp.events_delivered; stats->agc_mismatches = rp.agc_mismatches;

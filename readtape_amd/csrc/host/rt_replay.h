@@ -125,6 +125,14 @@ int rt_replay_run_after_deskew(const struct rt_options *opt, const struct rt_par
 /* -textfile: the next decode this thread starts (rt_replay_run, _run_named, _run_after_deskew, _run_ww, _run_ww_detector) writes the interpreted text
  * file of <base> in the verbose layout beside its .tap; o->ntrks is taken from the decode.  o == NULL takes the request back. */
 void rt_replay_set_text(const rt_text_options *o, const char *base, const char *created);
+/* --peakstats: the next decode this thread starts (rt_replay_run, _run_named, _run_after_deskew, _run_ww, _run_ww_detector, with the rt_replay_deskew
+ * pre-pass in front of it) gathers the reference's flux-transition statistics in its main pass too, writes <base>.peakstats.csv - and a pre-pass
+ * <base>.peakstats_deskew.csv - and logs the head-skew verdict under the summary.  quiet: the reference's -q (only the _deskew file, no log lines);
+ * deskew: its `deskew` flag (-deskew or -skew= was given: picks the sentence).  base == NULL takes the request back and forgets the results.
+ * rt_replay_get_peakstats(which: 0 the decode's, 1 the pre-pass'): the histogram behind the file (counts[RT_MAXTRKS][RT_PEAKSTAT_BUCKETS],
+ * trksums[RT_MAXTRKS]) and skew_compute_deskew's answer, of the last such decode on this thread; 0 if there is none. */
+void rt_replay_set_peakstats(const char *base, int quiet, int deskew);
+int  rt_replay_get_peakstats(int which, float *leftbin, float *binwidth, int32_t *counts, int32_t *trksums, int *ok, float *peak_frac, float *stddev_frac);
 
 #ifdef __cplusplus
 }

@@ -158,7 +158,8 @@ def plan_windows(raw_rows, window_rows, halo_rows, subsample=1, skip=0, ramp=Tru
 
 def decode_file_streaming(path, tap_path, window_rows=1 << 24, halo_rows=1 << 17, opts: pipeline.DecodeOptions | None = None, cfgkw=None,
                           device="cuda:0", replay_threads: int = 1, read_threads: int = 4, replay_split: int = 1, scan_contexts: int = 3, ramp: bool = True,
-                          subsample: int = 1, skip: int = 0, deskew: bool = False, skew=None, prepass_rows: int = 1 << 22):
+                          subsample: int = 1, skip: int = 0, deskew: bool = False, skew=None, prepass_rows: int = 1 << 22,
+                          peakstats: bool = False):
     """Decodes the .tbin file `path` to the SIMH file `tap_path` through device windows of `window_rows` rows (a multiple of 1024).
     Returns statistics incl. the end-to-end rate (disk -> .tap), the time spent in the host replay and the rows the halos re-read.
     replay_threads > 1: the windows' host replays run side by side (fragments are independent: each has its own decoder context
@@ -184,6 +185,7 @@ def decode_file_streaming(path, tap_path, window_rows=1 << 24, halo_rows=1 << 17
     statistics["bpi"], ["skew"]: what the scans ran with.  With the defaults and a header that states its density nothing of this costs a launch or a buffer."""
     import queue
     import torch
+    pipeline.refuse_peakstats(peakstats, "ingest.decode_file_streaming")
     assert window_rows % 1024 == 0
     t_enter = time.perf_counter()
     opts = opts or pipeline.DecodeOptions()

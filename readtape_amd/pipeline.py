@@ -259,7 +259,8 @@ def decode_tape(hdr, rows, tap_path, log_path=None, opts: DecodeOptions | None =
                 skew=None, invert=False, parms_text: str | None = None, find_zeros=False, evt_path=None, differentiate=False,
                 subsample: int = 1, deskew: bool = False, deskew_prefix_rows: int = 1 << 22, trkorder: str | None = None,
                 out_base: str | None = None, in_name: str | None = None, tap_format: bool = True, fluxdir: str = "neg", reverse: bool = False,
-                textfile=None, created=None, labels: bool = False, blklimit: int | None = None, skip: int = 0):
+                textfile=None, created=None, labels: bool = False, blklimit: int | None = None, skip: int = 0,
+                peakstats: bool = False, quiet: bool = False):
     """Decodes one tape; returns (stats dict, ScanResult).  `fe_factory(cfg)` builds the front end
     (default: the GPU one; tests/cpu_emul passes the emulated library).
     Output: tap_path = one SIMH .tap file; or out_base = the reference's own naming - <out_base>.tap, or with tap_format=False
@@ -270,7 +271,12 @@ def decode_tape(hdr, rows, tap_path, log_path=None, opts: DecodeOptions | None =
     labels: IBM standard labels (VOL1, HDR1/2, EOF1/2, EOV1/2; src/ibmlabels.c) are logged and, without tap_format, absorbed, the data files
     named <out_base>-NNN-<dsid>.bin - the reference's default, its -nolabels is labels=False.  blklimit: the reference's -blklimit=n, the
     decode stops once n blocks are written.  skip: the reference's -skip=n - the first n raw rows are not part of the tape (before
-    -subsample; the time base starts at the header's tstart on the first row used, as in ingest.decode_file_streaming)."""
+    -subsample; the time base starts at the header's tstart on the first row used, as in ingest.decode_file_streaming).
+    peakstats: the reference's flux-transition statistics - the decoders bin every transition against their clock in the decode itself (not only in the
+    -deskew pre-pass), <base>.peakstats.csv is written (base = out_base, or tap_path without its extension; a pre-pass also writes
+    <base>.peakstats_deskew.csv) and the head-skew verdict is logged under the summary (src/readtape.c:2045-2058).  stats["peakstats"] and, where a
+    pre-pass ran, stats["peakstats_deskew"] hold leftbin, binwidth, counts [ntrks, 50], trksums and path; stats["skew_ok"], ["skew_peak_frac"] and
+    ["skew_stddev_frac"] are the verdict.  quiet: the reference's -q - only the _deskew file, no log lines."""
     opts = opts or DecodeOptions()
     if skip:
         if skip < 0 or skip > int(rows.shape[0]):                          # "endfile with %d lines left to skip" (src/readtape.c:1641)
@@ -281,7 +287,8 @@ def decode_tape(hdr, rows, tap_path, log_path=None, opts: DecodeOptions | None =
     if hdr.mode == tbin.MODE_WW:                                           # one chain per tape, detector state handed back and forth: its own path
         st = decode_tape_ww(hdr, rows, tap_path, log_path=log_path, order=trkorder, verbose=opts.verbose, evt_path=evt_path, fe_factory=fe_factory,
                             invert=invert, out_base=out_base, in_name=in_name, deskew=deskew, fluxdir=fluxdir, reverse=reverse,      # (-fluxdir, -reverse: Whirlwind only)
-                            find_zeros=find_zeros, differentiate=differentiate, textfile=textfile, created=created, labels=labels, blklimit=blklimit)
+                            find_zeros=find_zeros, differentiate=differentiate, textfile=textfile, created=created, labels=labels, blklimit=blklimit,
+                            peakstats=peakstats, quiet=quiet)
         return st, None
     lib = _load_decode_lib()
     if trkorder:                                                           # -order= wins over the header's TBINORD extension (src/readtape.c:1346-1355)
@@ -319,44 +326,49 @@ def decode_tape(hdr, rows, tap_path, log_path=None, opts: DecodeOptions | None =
                  revparity=opts.revparity, do_correction=int(opts.correct), find_zeros=int(find_zeros), do_differentiate=int(differentiate),
                  multiple_tries=int(opts.multiple_tries), tap_format=1, add_parity=int(opts.add_parity), verbose=int(opts.verbose))
     calibrated = deskew and skew is None and mode != tbin.MODE_PE        # "-deskew option is ignored for PE", src/readtape.c:1677
-    if calibrated:
-        skew = calibrate_deskew(hdr, rows, full, o, fe_factory, invert=invert, find_zeros=find_zeros, differentiate=differentiate,
-                                log_path=log_path, evt_path=evt_path, first_prefix_rows=deskew_prefix_rows, append=detected, **bpi_kw)
-        cfg = frontend.FrontEndConfig.from_header(hdr, parmsets=frontend_parmsets(full), skew=skew, invert=invert, find_zeros=find_zeros, differentiate=differentiate, **bpi_kw)
-    fe = (fe_factory or frontend.FrontEnd)(cfg)
-    res = fe.scan(rows).fetch()
-    nrows = int(rows.shape[0])
+    peak_base = _request_peakstats(lib, peakstats, out_base, tap_path, quiet, bool(deskew) or skew is not None)
+    try:                                                                   # (whatever happens, the request does not outlive this decode)
+        if calibrated:
+            skew = calibrate_deskew(hdr, rows, full, o, fe_factory, invert=invert, find_zeros=find_zeros, differentiate=differentiate,
+                                    log_path=log_path, evt_path=evt_path, first_prefix_rows=deskew_prefix_rows, append=detected, **bpi_kw)
+            cfg = frontend.FrontEndConfig.from_header(hdr, parmsets=frontend_parmsets(full), skew=skew, invert=invert, find_zeros=find_zeros, differentiate=differentiate, **bpi_kw)
+        fe = (fe_factory or frontend.FrontEnd)(cfg)
+        res = fe.scan(rows).fetch()
+        nrows = int(rows.shape[0])
 
-    o = _Options(mode=mode, ntrks=hdr.ntrks, bpi=cfg.bpi, ips=cfg.ips, specified_parity=0 if opts.even_parity else 1,
-                 revparity=opts.revparity, do_correction=int(opts.correct), find_zeros=int(find_zeros), do_differentiate=int(differentiate),
-                 multiple_tries=int(opts.multiple_tries), tap_format=int(tap_format), add_parity=int(opts.add_parity), verbose=int(opts.verbose))
-    parr = (_Parms * len(full))(*full)
-    W = (C.c_int * len(full))(*fe.widths)
-    exact, free, keep = _exact_callbacks(fe, rows, hdr.ntrks, fe_factory)
+        o = _Options(mode=mode, ntrks=hdr.ntrks, bpi=cfg.bpi, ips=cfg.ips, specified_parity=0 if opts.even_parity else 1,
+                     revparity=opts.revparity, do_correction=int(opts.correct), find_zeros=int(find_zeros), do_differentiate=int(differentiate),
+                     multiple_tries=int(opts.multiple_tries), tap_format=int(tap_format), add_parity=int(opts.add_parity), verbose=int(opts.verbose))
+        parr = (_Parms * len(full))(*full)
+        W = (C.c_int * len(full))(*fe.widths)
+        exact, free, keep = _exact_callbacks(fe, rows, hdr.ntrks, fe_factory)
 
-    _request_text(lib, textfile, out_base, tap_path, created)
-    _request_run(lib, labels, blklimit)
-    st = _Stats()
-    bursts = np.ascontiguousarray(res.bursts)
-    counts = np.ascontiguousarray(res.counts)
-    events = res._events
-    if out_base:
-        rc = lib.rt_replay_run_named(C.byref(o), parr, len(full), hdr.tdelta_ns, hdr.tstart_ns, nrows, 0, W,
-                                     bursts.ctypes.data, len(bursts), counts.ctypes.data, events.ctypes.data, exact, free, None,
-                                     out_base.encode(), (in_name or out_base + ".tbin").encode(), log_path.encode() if log_path else None,
-                                     evt_path.encode() if evt_path else None, int(calibrated or detected), C.byref(st))
-    else:
-        run = lib.rt_replay_run_after_deskew if (calibrated or detected) else lib.rt_replay_run      # (continues the pre-passes' log / event dump)
-        rc = run(C.byref(o), parr, len(full), hdr.tdelta_ns, hdr.tstart_ns, nrows, 0, W,
-                 bursts.ctypes.data, len(bursts), counts.ctypes.data, events.ctypes.data,
-                 exact, free, None,
-                 tap_path.encode() if tap_path else None, log_path.encode() if log_path else None,
-                 evt_path.encode() if evt_path else None, C.byref(st))
-    lib.rt_driver_set_run(0, -1)                                          # (a run that never reached its blocks leaves nothing behind for the next)
-    _release(keep)
+        _request_text(lib, textfile, out_base, tap_path, created)
+        _request_run(lib, labels, blklimit)
+        st = _Stats()
+        bursts = np.ascontiguousarray(res.bursts)
+        counts = np.ascontiguousarray(res.counts)
+        events = res._events
+        if out_base:
+            rc = lib.rt_replay_run_named(C.byref(o), parr, len(full), hdr.tdelta_ns, hdr.tstart_ns, nrows, 0, W,
+                                         bursts.ctypes.data, len(bursts), counts.ctypes.data, events.ctypes.data, exact, free, None,
+                                         out_base.encode(), (in_name or out_base + ".tbin").encode(), log_path.encode() if log_path else None,
+                                         evt_path.encode() if evt_path else None, int(calibrated or detected), C.byref(st))
+        else:
+            run = lib.rt_replay_run_after_deskew if (calibrated or detected) else lib.rt_replay_run      # (continues the pre-passes' log / event dump)
+            rc = run(C.byref(o), parr, len(full), hdr.tdelta_ns, hdr.tstart_ns, nrows, 0, W,
+                     bursts.ctypes.data, len(bursts), counts.ctypes.data, events.ctypes.data,
+                     exact, free, None,
+                     tap_path.encode() if tap_path else None, log_path.encode() if log_path else None,
+                     evt_path.encode() if evt_path else None, C.byref(st))
+        lib.rt_driver_set_run(0, -1)                                          # (a run that never reached its blocks leaves nothing behind for the next)
+        _release(keep)
+    finally:
+        peaks = _collect_peakstats(lib, peak_base, hdr.ntrks, quiet)
     if rc != 0:
         raise RuntimeError("rt_replay_run failed")
     stats = {k: getattr(st, k) for k, _ in _Stats._fields_}
+    stats.update(peaks)
     if stats["reference_fatal"]:
         raise ReferenceFatal(f"AGC gain bad in lookfor_peak on track {stats['fatal_trk']} at sample {stats['fatal_row']}: the reference asserts and exits "
                              "here (src/decoder.c:782); the blocks in front of it are in the .tap", stats)
@@ -385,6 +397,41 @@ def _request_text(lib, opts, out_base, tap_path, created):
     lib.rt_replay_set_text(C.byref(o), os.fsencode(base), tf._created(created))
 
 
+def _request_peakstats(lib, on, out_base, tap_path, quiet, deskew):
+    """peakstats=True for the decode that is about to start on this thread, its -deskew pre-pass included (rt_replay_set_peakstats).
+    -> the base name of the files, or None"""
+    lib.rt_replay_set_peakstats.argtypes = [C.c_char_p, C.c_int, C.c_int]
+    if not on:
+        lib.rt_replay_set_peakstats(None, 0, 0)                           # (a decode that died before its blocks leaves no request behind)
+        return None
+    base = out_base or (os.path.splitext(tap_path)[0] if tap_path else None)
+    if base is None:
+        raise ValueError("peakstats: give out_base or tap_path, the statistics files are named after it")
+    lib.rt_replay_set_peakstats(os.fsencode(base), int(bool(quiet)), int(bool(deskew)))
+    return base
+
+
+def _collect_peakstats(lib, base, ntrks, quiet):
+    """What the decode that just ended on this thread left of its statistics (rt_replay_get_peakstats) -> the entries of the stats dict; the request is taken back."""
+    if base is None:
+        return {}
+    out = {}
+    lib.rt_replay_get_peakstats.argtypes = [C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.POINTER(C.c_int),
+                                            C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    for which, key, suffix in ((0, "peakstats", ""), (1, "peakstats_deskew", "_deskew")):
+        counts, sums = np.zeros((19, 50), np.int32), np.zeros(19, np.int32)
+        left, width, ok, pf, sf = C.c_float(0), C.c_float(0), C.c_int(0), C.c_float(0), C.c_float(0)
+        if not lib.rt_replay_get_peakstats(which, C.byref(left), C.byref(width), counts.ctypes.data, sums.ctypes.data, C.byref(ok), C.byref(pf), C.byref(sf)):
+            continue
+        path = f"{base}.peakstats{suffix}.csv"
+        out[key] = dict(leftbin=float(left.value), binwidth=float(width.value), counts=counts[:ntrks].copy(), trksums=sums[:ntrks].copy(),
+                        path=path if (which == 1 or not quiet) else None)
+        if which == 0:
+            out.update(skew_ok=bool(ok.value), skew_peak_frac=float(pf.value), skew_stddev_frac=float(sf.value))
+    lib.rt_replay_set_peakstats(None, 0, 0)
+    return out
+
+
 def _request_run(lib, labels, blklimit):
     """labels= and blklimit= for the decode that is about to start on this thread (rt_driver_set_run)."""
     if blklimit is not None and blklimit < 0:
@@ -395,13 +442,15 @@ def _request_run(lib, labels, blklimit):
 
 def decode_tape_ww(hdr, rows, tap_path, log_path=None, order: str | None = None, fluxdir: str = "neg", reverse: bool = False, verbose: bool = True,
                    evt_path=None, fe_factory=None, invert=False, chunk_rows: int = 4096, out_base=None, in_name=None, deskew: bool = False,
-                   find_zeros: bool = False, differentiate: bool = False, textfile=None, created=None, labels: bool = False, blklimit: int | None = None):
+                   find_zeros: bool = False, differentiate: bool = False, textfile=None, created=None, labels: bool = False, blklimit: int | None = None,
+                   peakstats: bool = False, quiet: bool = False):
     """Decodes a Whirlwind tape (6 tracks, 100 BPI; mode WW in the header or by the caller).  order = the heads' roles (-order=CMLcml,
     default: the header's TBINORD string); fluxdir neg / pos / auto.  The device detector keeps its state across block attempts, so
     the host replay fetches its events in chunks and hands the state back in (rtfe_ww_scan).  deskew: the reference's
     -deskew (a pre-pass over the first blocks learns every head's delay and the pulse heights, src/readtape.c:1676-1716; the delays
     come back as stats["skew_delays"]).  find_zeros / differentiate: the reference's -zeros / -differentiate - the zero-crossing detectors and
-    the peak detector on the differentiated signal (rtfe_ww_detector_scan); the front end picks the state kind from them.  Returns the statistics."""
+    the peak detector on the differentiated signal (rtfe_ww_detector_scan); the front end picks the state kind from them.  peakstats, quiet: as in
+    decode_tape (the clock pulses' ends against the primary clock's last pulse end).  Returns the statistics."""
     lib = _load_decode_lib()
     order = order or hdr.trkorder or "CMLcml"
     if len(order) != hdr.ntrks:
@@ -448,6 +497,7 @@ def decode_tape_ww(hdr, rows, tap_path, log_path=None, order: str | None = None,
     cb = _WW_SCAN_FN(scan)
     _request_text(lib, textfile, out_base, tap_path, created)
     _request_run(lib, labels, blklimit)
+    peak_base = _request_peakstats(lib, peakstats, out_base, tap_path, quiet, bool(deskew))
     st = _Stats()
     init = fe.ww_initial_state()
     delays = (C.c_int * hdr.ntrks)()
@@ -457,11 +507,13 @@ def decode_tape_ww(hdr, rows, tap_path, log_path=None, order: str | None = None,
                               evt_path.encode() if evt_path else None, C.byref(st), int(bool(deskew)), delays)
     lib.rt_driver_set_run(0, -1)
     fe.close()
+    peaks = _collect_peakstats(lib, peak_base, hdr.ntrks, quiet)
     if rc == -2 and not bad:
         raise RuntimeError("the -deskew pre-pass found tracks without flux transitions (is the order string right?)")
     if rc != 0:
         raise RuntimeError(f"rt_replay_run_ww_detector failed ({rc}, {bad[:2]})")
     stats = {k: getattr(st, k) for k, _ in _Stats._fields_}
+    stats.update(peaks)
     if deskew:
         stats["skew_delays"] = list(delays)
     if stats["reference_fatal"]:
@@ -479,6 +531,14 @@ def decode_tape_ww(hdr, rows, tap_path, log_path=None, order: str | None = None,
 # whole tape's; the end-of-medium marker goes behind the last one.  (SURVEY.md 8e "Host side".)
 # ---------------------------------------------------------------------------------------------------------------------
 I64MAX = (1 << 63) - 1
+
+
+def refuse_peakstats(peakstats, who):
+    """The fragment, stream and shard decodes gather no flux-transition statistics: the bins are fixed by the tape's first recorded transition, which only
+    the first fragment sees."""
+    if peakstats:
+        raise ValueError(f"{who}: peakstats is for the resident decode (pipeline.decode_tape, decode_tape_ww) - the histogram's bins are fixed by the "
+                         "tape's first recorded transition, which only the first fragment sees")
 
 
 def scan_fragment(fe, rows_with_halo, own_rows, lo, is_first, is_last, stream=None, raw=None):
@@ -502,10 +562,11 @@ def scan_fragment(fe, rows_with_halo, own_rows, lo, is_first, is_last, stream=No
 
 
 def decode_fragment(hdr, cfg, fe, res, rows_with_halo, lo, start_row, stop_row, tap_path, full, opts, fe_factory=None, log_path=None, evt_path=None,
-                    exact_lock=None):
+                    exact_lock=None, peakstats: bool = False):
     """Host replay of one scanned fragment -> its piece of the .tap (no end marker).  Returns the replay statistics.
     exact_lock: several fragments are replayed side by side and share `fe` for their exact rescans: one at a time."""
     from readtape_amd import shard
+    refuse_peakstats(peakstats, "decode_fragment")
     lib = _load_decode_lib()
     o = _Options(mode=hdr.mode, ntrks=hdr.ntrks, bpi=cfg.bpi, ips=cfg.ips, specified_parity=0 if opts.even_parity else 1,
                  revparity=opts.revparity, do_correction=int(opts.correct), find_zeros=int(cfg.find_zeros), do_differentiate=int(cfg.differentiate),
@@ -530,10 +591,12 @@ def decode_fragment(hdr, cfg, fe, res, rows_with_halo, lo, start_row, stop_row, 
     return stats
 
 
-def decode_fragments(hdr, cfg, fe, res, rows_with_halo, lo, start_rows, stop_rows, tap_paths, full, opts, fe_factory=None, exact_lock=None):
+def decode_fragments(hdr, cfg, fe, res, rows_with_halo, lo, start_rows, stop_rows, tap_paths, full, opts, fe_factory=None, exact_lock=None,
+                     peakstats: bool = False):
     """decode_fragment for several fragments of ONE scan side by side - native threads inside librtdecode.so, this thread takes the first
     (rt_replay_run_fragments): the streaming reader hands a window's sub-fragments over in one call.  Returns [(statistics, seconds), ...]."""
     from readtape_amd import shard
+    refuse_peakstats(peakstats, "decode_fragments")
     lib = _load_decode_lib()
     o = _Options(mode=hdr.mode, ntrks=hdr.ntrks, bpi=cfg.bpi, ips=cfg.ips, specified_parity=0 if opts.even_parity else 1,
                  revparity=opts.revparity, do_correction=int(opts.correct), find_zeros=int(cfg.find_zeros), do_differentiate=int(cfg.differentiate),
@@ -564,10 +627,12 @@ def decode_fragments(hdr, cfg, fe, res, rows_with_halo, lo, start_rows, stop_row
     return out
 
 
-def decode_tape_fragments(hdr, rows, tap_path, spans, opts: DecodeOptions | None = None, fe_factory=None, halo_rows=1 << 16, cfgkw=None):
+def decode_tape_fragments(hdr, rows, tap_path, spans, opts: DecodeOptions | None = None, fe_factory=None, halo_rows=1 << 16, cfgkw=None,
+                          peakstats: bool = False):
     """Decodes one resident tape as the fragments `spans` = [(lo, hi), ...] (contiguous, cuts on the 64-row grid), one after the other
     on this process' device, and concatenates their .tap pieces: what N ranks do with shard.plan_shards + the halo exchange, and what
     the streaming reader does window by window.  Returns a list of per-fragment statistics."""
+    refuse_peakstats(peakstats, "decode_tape_fragments")
     opts = opts or DecodeOptions()
     full = default_parmsets(hdr.mode, opts.nparmsets or (15 if opts.multiple_tries else 1))
     cfg = frontend.FrontEndConfig.from_header(hdr, parmsets=frontend_parmsets(full), **(cfgkw or {}))

@@ -275,7 +275,7 @@ def _decode_shards(who, hdr, sr, lo, n_total, lens, rank, world, dist, tap_path,
 
 
 def decode_sharded(hdr, own, lo: int, n_total: int, rank: int, world: int, dist, tap_path: str | None, opts=None, fe_factory=None,
-                   halo_rows: int = 1 << 16, cfgkw=None, deskew: bool = False, skew=None):
+                   halo_rows: int = 1 << 16, cfgkw=None, deskew: bool = False, skew=None, peakstats: bool = False):
     """The whole multi-rank decode of ONE tape: `own` = this rank's rows [lo, lo + len(own)) of the n_total-row tape.
       1. halo exchange (isend/irecv; repeated with a four times longer halo - it may then span several of the ranks behind - while some
          rank's last own burst runs past it; the halo stops growing at the tape's end, so the loop ends),
@@ -289,6 +289,7 @@ def decode_sharded(hdr, own, lo: int, n_total: int, rank: int, world: int, dist,
     calibrate_deskew on ITS OWN rows and broadcasts what they find; where their stopping rule is not met inside rank 0's rows and other ranks hold
     more, every rank raises a RuntimeError (pass the values in cfgkw / skew, or start from the file: decode_file_sharded reads a longer prefix)."""
     from . import frontend, ingest, pipeline
+    pipeline.refuse_peakstats(peakstats, "shard.decode_sharded")
     opts = opts or pipeline.DecodeOptions()
     full = pipeline.default_parmsets(hdr.mode, opts.nparmsets or (15 if opts.multiple_tries else 1))
     cfgkw = dict(cfgkw or {})
@@ -313,6 +314,20 @@ def decode_sharded(hdr, own, lo: int, n_total: int, rank: int, world: int, dist,
                           fe_factory is not None, halo_rows)[0]
 
 
+def _refusing_peakstats(fn):
+    """fn with one keyword more, peakstats (False): True raises pipeline.refuse_peakstats' ValueError before anything is read or exchanged.  The function's
+    own parameter list stays what its callers and tests/test_shard_file_plan.py know (inspect.signature follows __wrapped__)."""
+    import functools
+
+    @functools.wraps(fn)
+    def wrapper(*args, peakstats: bool = False, **kw):
+        from . import pipeline
+        pipeline.refuse_peakstats(peakstats, "shard." + fn.__name__)
+        return fn(*args, **kw)
+    return wrapper
+
+
+@_refusing_peakstats
 def decode_file_sharded(path, tap_path, rank: int, world: int, dist, opts=None, cfgkw=None, halo_rows: int = 1 << 16, subsample: int = 1, skip: int = 0,
                         deskew: bool = False, skew=None, prepass_rows: int = 1 << 22, device="cuda:0", align: int = 1024, fe_factory=None,
                         _lib_path=None, _backend=None):
