@@ -95,6 +95,10 @@ options:
                  file of the list, otherwise each file's own name follows -outp=
   --stream       decode a .tbin through device windows instead of reading it whole
                  (needs -tap and -nolabels; not for Whirlwind, -textfile or -blklimit; no log)
+  --windows[=n]  decode a .tbin through device windows [of n rows] with everything the whole-file
+                 decode writes: the log, labels and label-named files, numbered .bin files,
+                 -textfile, -blklimit, -order/-bpi/-ips, --peakstats (not for Whirlwind, a .csv
+                 input, or together with --stream)
   --peakstats    write <basefilename>.peakstats.csv (and, with -deskew, .peakstats_deskew.csv):
                  per track, where the flux transitions fall against the decoder's clock; and
                  say under the summary whether the head skew is significant (-q: only the
@@ -165,6 +169,7 @@ class Options:
     multiple_tries: bool = True
     filelist: bool = False
     stream: bool = False
+    windows: int | None = None         # --windows[=rows]: None not given, 0 the window --stream computes
     peakstats: bool = False
 
     def text_options(self):
@@ -319,6 +324,13 @@ def parse_option(o: Options, option: str) -> bool:
         return True
     if up == "-PEAKSTATS":
         o.peakstats = True
+        return True
+    if up == "-WINDOWS":
+        o.windows = 0
+        return True
+    ok, n = _int(arg, "-WINDOWS=", 1024, 1 << 30)
+    if ok:
+        o.windows = -(-n // 1024) * 1024                      # (windows are cut on the 1024-row grid)
         return True
     ok, n = _int(arg, "NTRKS=", MINTRKS, MAXTRKS)
     if ok:
@@ -503,6 +515,27 @@ def _stream_refusal(o: Options, mode):
     return None
 
 
+def _stream_window(o: Options, path):
+    """the window --stream and --windows take by default (a short file: no buffers for windows it does not have) -> (window rows, halo rows)"""
+    from . import ingest
+    used = max(0, ingest._payload_geometry(path)[2] - o.skip) // o.subsample
+    window = min(1 << 24, max(1024, -(-used // 1024) * 1024))
+    return window, min(1 << 17, window)
+
+
+def _decode_windows(o: Options, path, hdr, mode, out_base, log_path, parms_text, text_opts):
+    """--windows: the file through ingest.decode_file_windows with the options as the resident path takes them -> its statistics"""
+    from . import ingest
+    window, halo = _stream_window(o, path)
+    if o.windows:
+        window, halo = o.windows, min(1 << 17, o.windows)
+    cfgkw = {k: v for k, v in (("invert", o.invert), ("find_zeros", o.find_zeros), ("differentiate", o.differentiate)) if v}
+    return ingest.decode_file_windows(path, out_base=out_base, log_path=log_path, tap_format=o.tap_format, labels=o.labels, blklimit=o.blklimit, textfile=text_opts,
+                                      peakstats=o.peakstats, quiet=o.quiet, hdr_overrides=dict(order=o.order or None, bpi=hdr.bpi, ips=hdr.ips, mode=mode),
+                                      in_name=path, parms_text=parms_text, window_rows=window, halo_rows=halo, opts=_decode_options(o), cfgkw=cfgkw or None,
+                                      subsample=o.subsample, skip=o.skip, deskew=o.deskew and o.skew is None, skew=o.skew)
+
+
 def decode_file(o: Options, name, fe_factory, out, outbase_of):
     """One tape: §3-§4 of the module's grammar.  -> True if every block was clean ("ok")."""
     from . import csvin, pipeline
@@ -512,7 +545,7 @@ def decode_file(o: Options, name, fe_factory, out, outbase_of):
     _say(out, o, f"\nreading file \"{path}\"\nthe output files will be \"{out_base}.xxx\"\n")
     hdr = rows = None
     if kind == "tbin":
-        if o.stream:
+        if o.stream or o.windows is not None:
             try:
                 hdr, _ = tbin.read_header(path)
             except (OSError, ValueError) as e:
@@ -537,6 +570,11 @@ def decode_file(o: Options, name, fe_factory, out, outbase_of):
     if mode == tbin.MODE_WW and o.multiple_tries:
         raise fatal("Sorry, multiple decoding tries is not implemented yet for Whirlwind")
     text_opts = o.text_options()
+    if o.windows is not None:
+        why = ("--stream and --windows are two decodes: give one" if o.stream else "--windows reads a .tbin file" if kind != "tbin" else
+               "--windows is not for Whirlwind tapes (one chain, no independent windows)" if mode == tbin.MODE_WW else None)
+        if why:
+            raise CliExit(2, why + "\n")
     if o.stream:
         why = "--stream reads a .tbin file" if kind != "tbin" else _stream_refusal(o, mode)
         if o.peakstats:
@@ -567,10 +605,9 @@ def decode_file(o: Options, name, fe_factory, out, outbase_of):
         from . import ingest
         _say(out, o, "the streamed decode writes no log\n")
         cfgkw = {k: v for k, v in (("invert", o.invert), ("find_zeros", o.find_zeros), ("differentiate", o.differentiate)) if v}
-        used = max(0, ingest._payload_geometry(path)[2] - o.skip) // o.subsample
-        window = min(1 << 24, max(1024, -(-used // 1024) * 1024))            # (a short file: no buffers for windows it does not have)
+        window, halo = _stream_window(o, path)
         try:
-            st = ingest.decode_file_streaming(path, out_base + ".tap", window_rows=window, halo_rows=min(1 << 17, window), opts=_decode_options(o), cfgkw=cfgkw or None,
+            st = ingest.decode_file_streaming(path, out_base + ".tap", window_rows=window, halo_rows=halo, opts=_decode_options(o), cfgkw=cfgkw or None,
                                               subsample=o.subsample, skip=o.skip, deskew=o.deskew and o.skew is None, skew=o.skew)
         except NotImplementedError as e:
             raise CliExit(2, f"{e}\n")
@@ -584,11 +621,14 @@ def decode_file(o: Options, name, fe_factory, out, outbase_of):
         log_path = scratch
     try:
         try:
-            stats, _ = pipeline.decode_tape(hdr, rows, None, log_path=log_path, opts=_decode_options(o), fe_factory=fe_factory, skew=o.skew, invert=o.invert,
-                                            parms_text=parms_text, find_zeros=o.find_zeros, differentiate=o.differentiate, subsample=o.subsample,
-                                            deskew=o.deskew, trkorder=o.order or None, out_base=out_base, in_name=path, tap_format=o.tap_format,
-                                            fluxdir=o.fluxdir, reverse=o.reverse, textfile=text_opts, labels=o.labels, blklimit=o.blklimit, skip=o.skip,
-                                            peakstats=o.peakstats, quiet=o.quiet)
+            if o.windows is not None:
+                stats = _decode_windows(o, path, hdr, mode, out_base, log_path, parms_text, text_opts)
+            else:
+                stats, _ = pipeline.decode_tape(hdr, rows, None, log_path=log_path, opts=_decode_options(o), fe_factory=fe_factory, skew=o.skew, invert=o.invert,
+                                                parms_text=parms_text, find_zeros=o.find_zeros, differentiate=o.differentiate, subsample=o.subsample,
+                                                deskew=o.deskew, trkorder=o.order or None, out_base=out_base, in_name=path, tap_format=o.tap_format,
+                                                fluxdir=o.fluxdir, reverse=o.reverse, textfile=text_opts, labels=o.labels, blklimit=o.blklimit, skip=o.skip,
+                                                peakstats=o.peakstats, quiet=o.quiet)
         finally:
             if log_path and not o.quiet and os.path.exists(log_path):
                 with open(log_path, errors="replace") as f:

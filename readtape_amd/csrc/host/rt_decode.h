@@ -194,7 +194,12 @@ struct rt_dec {
     * to a histogram of transition distances instead of a block decoder */
    int     doing_density_detection;
    struct { int deltas[RT_ESTDEN_NUMBINS], counts[RT_ESTDEN_NUMBINS], binsused, totalcount, fatal; } estden;
-   struct { int initialized; float leftbin, binwidth; int counts[RT_MAXTRKS][RT_PEAKSTAT_BUCKETS]; int trksums[RT_MAXTRKS]; } peakstat;
+   struct { int initialized; float leftbin, binwidth; int counts[RT_MAXTRKS][RT_PEAKSTAT_BUCKETS]; int trksums[RT_MAXTRKS];
+            long long nraw; } peakstat;     /* (nraw: transitions peak_unbinned has put aside, in here so that an attempt's roll-back takes them back too) */
+   /* the windowed decode (rt_replay.c, the block journal): a fragment's histogram shares its bins with the other fragments' - while they are not known a
+    * transition is handed to peak_unbinned, which returns 1 once it has set the bins (the transition is then counted) and 0 if it kept the transition */
+   int   (*peak_unbinned)(struct rt_dec *d, float bitspacing, float peaktime, int trknum);
+   void   *peak_user;
    /* optional observer: called at the top of every up/down transition, before the format callback
     * (the same seam oracle/ref_event_shim.c wraps in the reference) */
    void  (*on_transition)(struct rt_dec *d, struct rt_trk *t, int is_top, void *user);
@@ -209,6 +214,11 @@ struct rt_dec {
    void  (*text_tapemark)(void *text, double timenow);
    /* IBM standard labels (src/ibmlabels.c; rt_driver_set_run): label blocks are logged, and without -tap absorbed, the data files named after HDR1 */
    int     labels, hdr1_seen;
+   /* the windowed decode: where rt_process_blocks would put a block out (rt_got_tapemark / rt_got_datablock) it hands it to on_block instead (blktype: the
+    * chosen attempt's); run_all_clean is its "all blocks clean so far" at that moment */
+   void  (*on_block)(struct rt_dec *d, enum rt_bstate blktype, void *user);
+   void   *on_block_user;
+   int     run_all_clean;
 };
 #define RT_PARM(d) ((d)->parmsets[(d)->parmset])
 
@@ -285,12 +295,20 @@ int rt_process_blocks(struct rt_dec *d, struct rt_reader *r, int blklimit);   /*
 /* For the next rt_process_blocks this thread starts (then forgotten, like rt_replay_set_text): labels != 0 turns the IBM label
  * handling on (the reference's default, off with -nolabels); blklimit >= 0 is the reference's -blklimit=n, < 0 none. */
 void rt_driver_set_run(int labels, int blklimit);
+/* the two ends of rt_process_blocks for a caller that puts blocks out without it (the journal's finisher): takes this thread's request (d->labels; -> the
+ * block limit, `blklimit` if none was asked for), and what follows the last block (the -blklimit line, the end of the output file) */
+int  rt_driver_take_run(struct rt_dec *d, int blklimit);
+void rt_end_of_blocks(struct rt_dec *d, int blklimit);
 
 /* ---- the -deskew pre-pass (src/readtape.c:1675-1717, NRZI and GCR): decodes the first blocks with no deskew while the
  * decoders record where each track's transitions fall, then turns the per-track averages into delays (in samples).
  * Returns the number of blocks used (>= 0), or -1 if some track saw no transition; *hit_end = 1 if the reader ran out
  * of data before the reference's stopping rule was met (the caller may then retry on a longer prefix of the tape). */
 void rt_record_peakstat(struct rt_dec *d, float bitspacing, float peaktime, int trknum);   /* src/decoder.c:136-173 */
+/* its parts: the bins the first transition fixes, a histogram started on given bins, one transition into it */
+void rt_peakstat_bins(enum rt_mode mode, float bitspacing, float *leftbin, float *binwidth);
+void rt_peakstat_start(struct rt_dec *d, float leftbin, float binwidth);
+void rt_peakstat_count(struct rt_dec *d, float peaktime, int trknum);
 #define RT_RECORDING_PEAKSTATS(d) ((d)->doing_deskew | (d)->want_peakstats)                /* the one test a decoder's record site costs */
 /* the report on them (want_peakstats): <peak_base>.peakstats<suffix>.csv (output_peakstats, src/decoder.c:175-214; returns 0 if it
  * could not be made), the two lines of numbers of skew_compute_deskew (src/decoder.c:243-281; returns its verdict and leaves it in

@@ -231,18 +231,30 @@ int rt_gcr_go_idle(struct rt_dec *d, struct rt_trk *t) {
 
 /* ---- flux-transition position statistics (src/decoder.c:136-173; the adjdeskew averages are experimental there
  *      and not restated) ---- */
-void rt_record_peakstat(struct rt_dec *d, float bitspacing, float peaktime, int trknum) {
-   if (!d->peakstat.initialized) {                            /* the first transition fixes the bins */
-      memset(&d->peakstat, 0, sizeof(d->peakstat));
-      const enum rt_mode m = d->opt.mode;
-      float range = bitspacing * (m == RT_NRZI ? 1.0f : m == RT_PE ? 1.2f : m == RT_GCR ? 3.0f : m == RT_WW ? 0.75f : 1.0f);
-      float bw = range / RT_PEAKSTAT_BUCKETS;
-      bw = (float)((int)(bw * 10e6 + 0.5) * 1e-6) / 10.0f;   /* to the nearest 0.1 usec (double product, int, double, float) */
-      float left = bitspacing - range / 2;
-      left = (float)(int)(left / bw) * bw;                   /* next lower multiple of the bin width */
-      d->peakstat.binwidth = bw; d->peakstat.leftbin = left;
-      d->peakstat.initialized = 1; }
+void rt_peakstat_bins(enum rt_mode m, float bitspacing, float *leftbin, float *binwidth) {
+   float range = bitspacing * (m == RT_NRZI ? 1.0f : m == RT_PE ? 1.2f : m == RT_GCR ? 3.0f : m == RT_WW ? 0.75f : 1.0f);
+   float bw = range / RT_PEAKSTAT_BUCKETS;
+   bw = (float)((int)(bw * 10e6 + 0.5) * 1e-6) / 10.0f;      /* to the nearest 0.1 usec (double product, int, double, float) */
+   float left = bitspacing - range / 2;
+   left = (float)(int)(left / bw) * bw;                      /* next lower multiple of the bin width */
+   *binwidth = bw; *leftbin = left; }
+
+void rt_peakstat_start(struct rt_dec *d, float leftbin, float binwidth) {
+   memset(&d->peakstat, 0, sizeof(d->peakstat));
+   d->peakstat.binwidth = binwidth; d->peakstat.leftbin = leftbin;
+   d->peakstat.initialized = 1; }
+
+void rt_peakstat_count(struct rt_dec *d, float peaktime, int trknum) {
    const int bucket = (int)((peaktime - d->peakstat.leftbin) / d->peakstat.binwidth);
    if (bucket < 0) ++d->peakstat.counts[trknum][0];
    else if (bucket >= RT_PEAKSTAT_BUCKETS) ++d->peakstat.counts[trknum][RT_PEAKSTAT_BUCKETS - 1];
    else { ++d->peakstat.counts[trknum][bucket]; ++d->peakstat.trksums[trknum]; } }
+
+void rt_record_peakstat(struct rt_dec *d, float bitspacing, float peaktime, int trknum) {
+   if (!d->peakstat.initialized) {                            /* the first transition fixes the bins */
+      if (d->peak_unbinned) { if (!d->peak_unbinned(d, bitspacing, peaktime, trknum)) return; }      /* (a fragment: the tape's first transition does, wherever it is) */
+      else {
+         float left, bw;
+         rt_peakstat_bins(d->opt.mode, bitspacing, &left, &bw);
+         rt_peakstat_start(d, left, bw); } }
+   rt_peakstat_count(d, peaktime, trknum); }

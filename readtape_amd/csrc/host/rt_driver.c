@@ -286,13 +286,19 @@ void rt_driver_set_run(int labels, int blklimit) {
 static void end_of_blocks(struct rt_dec *d, int blklimit) {      /* src/readtape.c:1884-1887 */
    if (d->numblks >= blklimit) rlog(d, "\n***blklimit=%d reached\n", blklimit);
    rt_tap_end(d); }
+void rt_end_of_blocks(struct rt_dec *d, int blklimit) { end_of_blocks(d, blklimit); }
 
-int rt_process_blocks(struct rt_dec *d, struct rt_reader *r, int blklimit) {
-   int all_clean = 1, out_of_data = 0;
+int rt_driver_take_run(struct rt_dec *d, int blklimit) {
    if (g_run_request.set) {
       g_run_request.set = 0;
       d->labels = g_run_request.labels;
       if (g_run_request.blklimit >= 0 && g_run_request.blklimit < blklimit) blklimit = g_run_request.blklimit; }
+   return blklimit; }
+
+int rt_process_blocks(struct rt_dec *d, struct rt_reader *r, int blklimit) {
+   int out_of_data = 0;
+   d->run_all_clean = 1;                                          /* (in the context, where on_block can read it) */
+   blklimit = rt_driver_take_run(d, blklimit);
    const int ww = d->opt.mode == RT_WW;
    d->interblock_counter = 0;
    if (ww && !d->ww_prepassed) rt_init_trackstate(d);             /* Whirlwind: once per tape - blocks may be one bit apart (src/readtape.c:1674); a -deskew pre-pass has done it */
@@ -311,7 +317,7 @@ int rt_process_blocks(struct rt_dec *d, struct rt_reader *r, int blklimit) {
          else out_of_data = !r->readblock(r->ctx, d->tries > 0);
          if (d->fatal) return 0;                                  /* the reference has exited (src/decoder.c:709-710,748,782): no other parameter set is tried */
          const struct rt_results *a = &d->results[d->parmset];
-         if (a->blktype == RT_BS_NONE) { end_of_blocks(d, blklimit); return all_clean; }      /* what was left of the data was no block */
+         if (a->blktype == RT_BS_NONE) { end_of_blocks(d, blklimit); return d->run_all_clean; }      /* what was left of the data was no block */
          ++d->tries;
          ++RT_PARM(d).tried;
          if (attempt_is_final(a)) {
@@ -325,11 +331,11 @@ int rt_process_blocks(struct rt_dec *d, struct rt_reader *r, int blklimit) {
          r->restore_pos(r->ctx);
          d->interblock_counter = 0; }
       if (!final) {
-         if (d->tries == 1) { if (d->results[d->parmset].errcount > 0) all_clean = 0; }
+         if (d->tries == 1) { if (d->results[d->parmset].errcount > 0) d->run_all_clean = 0; }
          else {
             int tier;
             const int pick = best_attempt(d, &tier);
-            if (tier > 0) all_clean = 0;
+            if (tier > 0) d->run_all_clean = 0;
             if (pick < 0) return 0;                                /* ("block state error in process_file()") */
             d->parmset = pick; } }
       if (d->results[d->parmset].blktype == RT_BS_NOISE) continue;
@@ -340,13 +346,15 @@ int rt_process_blocks(struct rt_dec *d, struct rt_reader *r, int blklimit) {
          rt_init_trackstate(d);
          out_of_data = !r->readblock(r->ctx, 1);
          if (d->fatal) return 0; }
-      switch (d->results[d->parmset].blktype) {
+      const enum rt_bstate got = d->results[d->parmset].blktype;
+      if (got != RT_BS_TAPEMARK && got != RT_BS_BLOCK && got != RT_BS_BADBLOCK) return 0;
+      if (d->on_block) { d->on_block(d, got, d->on_block_user); continue; }      /* (the windowed decode: the finisher puts it out, in tape order) */
+      switch (got) {
       case RT_BS_TAPEMARK: rt_got_tapemark(d); break;
       case RT_BS_BLOCK:    rt_got_datablock(d, 0); break;
-      case RT_BS_BADBLOCK: rt_got_datablock(d, 1); break;
-      default: return 0; } }
+      default:             rt_got_datablock(d, 1); break; } }
    end_of_blocks(d, blklimit);
-   return all_clean; }
+   return d->run_all_clean; }
 
 /* ---- the flux-transition statistics' report: <base>.peakstats[_deskew].csv and the head-skew verdict ---- */
 #define DESKEW_PEAKDIFF_WARNING 0.20      /* src/decoder.h:44-45: fractions of a bit (double literals, as there) */

@@ -19,6 +19,7 @@
 #include "rt_replay.h"
 
 #include <math.h>
+#include <pthread.h>
 #include <stdlib.h>
 #include <string.h>
 #include <time.h>
@@ -356,6 +357,7 @@ int rt_replay_readblock(void *ctx, int retry) {
    const int more = readblock_once(ctx, retry);
    /* src/readtape.c:1404 counts every pass of the read loop of a first attempt, the one that finds the end marker included */
    if (!retry) rp->d->lines_in += (rp->pos - from) + (more ? 0 : 1);
+   if (!retry && !more) rp->end_counted = 1;
    return more; }
 
 /* ---- the text file of the next decode (-textfile): asked for by rt_replay_set_text on the calling thread, taken by the run that
@@ -415,6 +417,132 @@ static void peak_report(struct rt_dec *d) {                      /* under the su
    peak_keep(d, 0);
    g_peak_request.set = 0; }
 
+/* ---------------------------------------------------------------------------------------------------------------------
+ * The block journal: a fragment's replay in journal mode puts no block out.  Where rt_process_blocks would call rt_got_tapemark /
+ * rt_got_datablock it appends a record of what those read from the context; the finisher (below, behind the fragment runners) takes the fragments'
+ * journals in tape order, puts each record back into ONE context and calls them there - block and file numbers, label state, the text file, -blklimit,
+ * the counters of the summary are sequential across the tape, and there is one copy of the output stage.  The format is private: host-endian structs in
+ * memory, read by nobody else.  (The PE, NRZI and GCR decoders write no log lines of their own; Whirlwind's, which do, is not decoded in fragments.)
+ * --------------------------------------------------------------------------------------------------------------------- */
+struct rt_peakbins { pthread_mutex_t mu; int have; float leftbin, binwidth; };      /* the histogram's bins, shared by a tape's fragments and its finisher */
+struct peak_raw { float bitspacing, peaktime; int32_t trk; };                        /* a transition recorded while the bins were not known */
+struct peak_counts { int32_t initialized; int32_t counts[RT_MAXTRKS][RT_PEAKSTAT_BUCKETS], trksums[RT_MAXTRKS]; int64_t nraw; };
+struct journal_work { int64_t attempts, exact_scans, chained, events_delivered, agc_mismatches; };
+#define JREC_MAGIC 0x4a524543u
+struct jrec {                      /* followed by ndata + nfaked uint16 words (the data, parity bit included; PE: the faked bits), then with has_snap a peak_counts */
+   uint32_t magic; int32_t blktype, parmset, tries, ndata, nfaked, all_clean, goodmultiple, has_snap, pad;
+   double timenow, t_blockstart;
+   int64_t end_abs, lines_in;                                 /* the absolute row behind the block's last attempt; the fragment's lines_in so far */
+   struct journal_work work;                                  /* the replay's counters so far */
+   int32_t tried[RT_MAXPARMSETS], chosen[RT_MAXPARMSETS];      /* so far, in this fragment */
+   struct rt_results res; };
+struct rt_journal {
+   unsigned char *buf; size_t len, cap; int nrec, failed;
+   struct rt_peakbins *bins; int first, snapshots;            /* bins != NULL: the fragment gathers peak statistics; first: it is the tape's first fragment */
+   struct peak_raw *raw; int64_t raw_cap;
+   /* what the fragment's replay left when it ended */
+   int done, all_clean, end_counted;
+   int64_t start_abs, final_abs, lines_in; double timenow;
+   int32_t tried[RT_MAXPARMSETS], chosen[RT_MAXPARMSETS], goodmultiple;
+   struct rt_replay_stats stats; struct peak_counts peak; };
+struct journal_hook { struct rt_journal *j; struct rt_replay *rp; };
+
+struct rt_peakbins *rt_peakbins_new(void) {
+   struct rt_peakbins *b = (struct rt_peakbins *)calloc(1, sizeof *b);
+   if (b) pthread_mutex_init(&b->mu, NULL);
+   return b; }
+void rt_peakbins_free(struct rt_peakbins *b) { if (b) { pthread_mutex_destroy(&b->mu); free(b); } }
+
+struct rt_journal *rt_journal_new(struct rt_peakbins *bins, int first, int snapshots) {
+   struct rt_journal *j = (struct rt_journal *)calloc(1, sizeof *j);
+   if (j) { j->bins = bins; j->first = first; j->snapshots = snapshots && bins; j->all_clean = 1; }
+   return j; }
+void rt_journal_free(struct rt_journal *j) { if (j) { free(j->buf); free(j->raw); free(j); } }
+int64_t rt_journal_bytes(const struct rt_journal *j) { return j ? (int64_t)(j->len + (size_t)j->raw_cap * sizeof(struct peak_raw)) : 0; }
+int rt_journal_records(const struct rt_journal *j) { return j ? j->nrec : 0; }
+int64_t rt_journal_final_row(const struct rt_journal *j) { return j && j->done ? j->final_abs : -1; }
+int rt_journal_stats(const struct rt_journal *j, struct rt_replay_stats *stats) { if (!j || !j->done || !stats) return -1; *stats = j->stats; return 0; }
+
+static void journal_put(struct rt_journal *j, const void *p, size_t n) {
+   if (j->failed) return;
+   if (j->len + n > j->cap) {
+      size_t cap = j->cap ? j->cap : 4096;
+      while (cap < j->len + n) cap *= 2;
+      unsigned char *nb = (unsigned char *)realloc(j->buf, cap);
+      if (!nb) { j->failed = 1; return; }
+      j->buf = nb; j->cap = cap; }
+   if (n) memcpy(j->buf + j->len, p, n);
+   j->len += n; }
+
+static void peak_counts_of(const struct rt_dec *d, struct peak_counts *p) {
+   p->initialized = d->peakstat.initialized; p->nraw = d->peakstat.nraw;
+   memcpy(p->counts, d->peakstat.counts, sizeof p->counts); memcpy(p->trksums, d->peakstat.trksums, sizeof p->trksums); }
+
+/* One block of the context `d` into the journal.  end_abs / work: what the replay knows (rt_journal_record: a caller without a replay gives zeros) */
+static void journal_record(struct rt_journal *j, struct rt_dec *d, enum rt_bstate blktype, int64_t end_abs, const struct journal_work *work) {
+   const struct rt_results *res = &d->results[d->parmset];
+   struct jrec r; memset(&r, 0, sizeof r);
+   r.magic = JREC_MAGIC; r.blktype = (int32_t)blktype; r.parmset = d->parmset; r.tries = d->tries;
+   r.ndata = blktype == RT_BS_BLOCK && res->minbits > 0 ? (res->minbits < RT_MAXBLOCK ? res->minbits : RT_MAXBLOCK) : 0;
+   r.nfaked = d->opt.mode == RT_PE ? r.ndata : 0;             /* (format_block_errors counts them) */
+   r.all_clean = d->run_all_clean; r.goodmultiple = d->numblks_goodmultiple; r.has_snap = j->snapshots;
+   r.timenow = d->timenow; r.t_blockstart = d->t_blockstart; r.end_abs = end_abs; r.lines_in = d->lines_in;
+   if (work) r.work = *work;
+   for (int i = 0; i < RT_MAXPARMSETS; ++i) { r.tried[i] = d->parmsets[i].tried; r.chosen[i] = d->parmsets[i].chosen; }
+   r.res = *res;
+   journal_put(j, &r, sizeof r);
+   journal_put(j, d->data, sizeof(uint16_t) * (size_t)r.ndata);
+   journal_put(j, d->data_faked, sizeof(uint16_t) * (size_t)r.nfaked);
+   if (r.has_snap) { struct peak_counts p; memset(&p, 0, sizeof p); peak_counts_of(d, &p); journal_put(j, &p, sizeof p); }
+   ++j->nrec; }
+void rt_journal_record(struct rt_journal *j, struct rt_dec *d, int blktype) { journal_record(j, d, (enum rt_bstate)blktype, 0, NULL); }
+void rt_journal_close(struct rt_journal *j) { if (j) { j->done = 1; j->all_clean = 1; } }
+
+static void journal_on_block(struct rt_dec *d, enum rt_bstate blktype, void *user) {
+   struct journal_hook *h = (struct journal_hook *)user;
+   const struct rt_replay *rp = h->rp;
+   const struct journal_work w = { rp->attempts, rp->exact_scans, rp->chained, rp->events_delivered, rp->agc_mismatches };
+   journal_record(h->j, d, blktype, rp->pos + rp->row_base, &w); }
+
+/* a transition while the fragment does not know the bins: the tape's first fragment fixes and publishes them, any other takes what is published - or
+ * keeps the transition until somebody has published (it never waits: the fragments may run in any order, on any number of threads, and the finisher,
+ * which goes through the journals in tape order, fixes the bins itself where a journal still holds transitions and nobody has) */
+static int journal_unbinned(struct rt_dec *d, float bitspacing, float peaktime, int trknum) {
+   struct rt_journal *j = (struct rt_journal *)d->peak_user;
+   struct rt_peakbins *B = j->bins;
+   float left, bw;
+   pthread_mutex_lock(&B->mu);
+   if (!B->have && j->first) { rt_peakstat_bins(d->opt.mode, bitspacing, &B->leftbin, &B->binwidth); B->have = 1; }
+   const int have = B->have;
+   left = B->leftbin; bw = B->binwidth;
+   pthread_mutex_unlock(&B->mu);
+   if (!have) {
+      if (d->peakstat.nraw >= j->raw_cap) {
+         const int64_t cap = j->raw_cap ? j->raw_cap * 2 : 4096;
+         struct peak_raw *nr = (struct peak_raw *)realloc(j->raw, sizeof(struct peak_raw) * (size_t)cap);
+         if (!nr) { j->failed = 1; return 0; }
+         j->raw = nr; j->raw_cap = cap; }
+      const struct peak_raw r = { bitspacing, peaktime, trknum };
+      j->raw[d->peakstat.nraw++] = r;
+      return 0; }
+   const int64_t n = d->peakstat.nraw;                        /* (an attempt's roll-back may bring them back: they stay where they are) */
+   rt_peakstat_start(d, left, bw);
+   for (int64_t i = 0; i < n; ++i) rt_peakstat_count(d, j->raw[i].peaktime, j->raw[i].trk);
+   return 1; }
+
+static void journal_attach(struct rt_dec *d, struct journal_hook *h) {
+   d->on_block = journal_on_block; d->on_block_user = h;
+   h->j->start_abs = h->rp->pos + h->rp->row_base;
+   if (h->j->bins) { d->want_peakstats = 1; d->peak_unbinned = journal_unbinned; d->peak_user = h->j; } }
+
+static void journal_close(struct rt_dec *d, struct journal_hook *h, int ok) {
+   struct rt_journal *j = h->j;
+   const struct rt_replay *rp = h->rp;
+   j->done = 1; j->all_clean = ok; j->end_counted = rp->end_counted;
+   j->final_abs = rp->pos + rp->row_base; j->lines_in = d->lines_in; j->timenow = d->timenow; j->goodmultiple = d->numblks_goodmultiple;
+   for (int i = 0; i < RT_MAXPARMSETS; ++i) { j->tried[i] = d->parmsets[i].tried; j->chosen[i] = d->parmsets[i].chosen; }
+   peak_counts_of(d, &j->peak); }
+
 /* prepass != NULL: run the -deskew pre-pass instead of the decode (no .tap); append: keep what is already in the log
  * and event-dump files (the decode that follows a pre-pass continues both, as the reference's single run does) */
 struct deskew_out { int *delays; int *nblks; int *hit_end; float *bpi, *implied; };
@@ -424,7 +552,7 @@ static int replay_any(const struct rt_options *opt, const struct rt_parms *parms
                   rt_exact_fn exact, rt_exact_free_fn exact_free, void *user,
                   const char *tap_path, const char *log_path, const char *evt_path, struct rt_replay_stats *stats,
                   int append, struct deskew_out *prepass, int64_t start_row, int64_t stop_row, int fragment,
-                  const char *out_base, const char *in_name) {
+                  const char *out_base, const char *in_name, struct rt_journal *jr) {
    const float sample_deltat = (float)tdelta_ns / 1e9f;              /* src/readtape.c:1345 */
    struct rt_dec *d = rt_dec_new(opt, sample_deltat, tdelta_ns);
    if (!d) return -1;
@@ -440,6 +568,7 @@ static int replay_any(const struct rt_options *opt, const struct rt_parms *parms
    rp.d = d; rp.ntrks = opt->ntrks; rp.nparm = nparm;
    for (int i = 0; i < nparm; ++i) rp.W[i] = W[i];
    rp.nrows = nrows; rp.row_base = row_base; rp.tstart_ns = tstart_ns; rp.tdelta_ns = tdelta_ns;
+   if (jr) rp.tstart_ns += row_base * tdelta_ns;      /* journal mode: the tape's own times (they are logged); a fragment's piece of a .tap holds none, and its clock starts with it */
    rp.bursts = bursts; rp.nbursts = nbursts; rp.counts = counts; rp.events = events;
    rp.exact = exact; rp.exact_free = exact_free; rp.exact_user = user;
    rp.find_zeros = opt->find_zeros;
@@ -460,8 +589,11 @@ static int replay_any(const struct rt_options *opt, const struct rt_parms *parms
       if (peaks && *prepass->nblks >= 0) peak_keep(d, 1); }
    else {
       if (!fragment) peaks = peak_attach(d);
-      struct rt_textfile *text = text_attach(d);
+      struct rt_textfile *text = jr ? NULL : text_attach(d);
+      struct journal_hook jh = { jr, &rp };
+      if (jr) journal_attach(d, &jh);
       ok = rt_process_blocks(d, &rd, 0x7fffffff);
+      if (jr) journal_close(d, &jh, ok);
       if (text) { d->text = NULL; d->text_record = NULL; d->text_tapemark = NULL; rt_text_close(text, 1); } }      /* src/readtape.c:1886 */
    if (in_name && !prepass) rt_write_summary(d, in_name, difftime(time(NULL), (time_t)wall0));
    if (peaks && !prepass) peak_report(d);
@@ -484,7 +616,7 @@ int rt_replay_run(const struct rt_options *opt, const struct rt_parms *parmsets,
                   rt_exact_fn exact, rt_exact_free_fn exact_free, void *user,
                   const char *tap_path, const char *log_path, const char *evt_path, struct rt_replay_stats *stats) {
    return replay_any(opt, parmsets, nparm, tdelta_ns, tstart_ns, nrows, row_base, W, bursts, nbursts, counts, events,
-                     exact, exact_free, user, tap_path, log_path, evt_path, stats, 0, NULL, 0, INT64_MAX, 0, NULL, NULL); }
+                     exact, exact_free, user, tap_path, log_path, evt_path, stats, 0, NULL, 0, INT64_MAX, 0, NULL, NULL, NULL); }
 
 /* One fragment of a tape (a time shard, or one window of a streamed file): rows are relative to the fragment's first row
  * (row_base = its absolute index; the bursts carry absolute rows).  The decode starts at start_row (0, or the start of the zone
@@ -498,36 +630,40 @@ int rt_replay_run_fragment(const struct rt_options *opt, const struct rt_parms *
                   const char *tap_path, const char *log_path, const char *evt_path, struct rt_replay_stats *stats,
                   int64_t start_row, int64_t stop_row) {
    return replay_any(opt, parmsets, nparm, tdelta_ns, tstart_ns, nrows, row_base, W, bursts, nbursts, counts, events,
-                     exact, exact_free, user, tap_path, log_path, evt_path, stats, 0, NULL, start_row, stop_row, 1, NULL, NULL); }
+                     exact, exact_free, user, tap_path, log_path, evt_path, stats, 0, NULL, start_row, stop_row, 1, NULL, NULL, NULL); }
 
 /* ---- fragments side by side: native threads (the caller is one Python thread per window, not one per fragment) ---- */
-#include <pthread.h>
 struct frag_job {
    const struct rt_options *opt; const struct rt_parms *parmsets; int nparm; int64_t tdelta_ns, tstart_ns, nrows, row_base; const int *W;
    const rtfe_burst *bursts; int64_t nbursts; const uint32_t *counts; const rtfe_event *events;
    rt_exact_fn exact; rt_exact_free_fn exact_free; void *user;
-   const char *tap_path; int64_t start_row, stop_row; struct rt_replay_stats *stats; double *seconds; int rc; };
+   const char *tap_path; int64_t start_row, stop_row; struct rt_replay_stats *stats; double *seconds; int rc; struct rt_journal *journal; };
 static void *frag_thread(void *p) {
    struct frag_job *j = (struct frag_job *)p;
    struct timespec a, b;
    clock_gettime(CLOCK_MONOTONIC, &a);
-   j->rc = rt_replay_run_fragment(j->opt, j->parmsets, j->nparm, j->tdelta_ns, j->tstart_ns, j->nrows, j->row_base, j->W, j->bursts, j->nbursts, j->counts, j->events,
-                                  j->exact, j->exact_free, j->user, j->tap_path, NULL, NULL, j->stats, j->start_row, j->stop_row);
+   if (j->journal)                                              /* journal mode: no piece of the .tap, the blocks go into the fragment's journal */
+      j->rc = replay_any(j->opt, j->parmsets, j->nparm, j->tdelta_ns, j->tstart_ns, j->nrows, j->row_base, j->W, j->bursts, j->nbursts, j->counts, j->events,
+                         j->exact, j->exact_free, j->user, NULL, NULL, NULL, &j->journal->stats, 0, NULL, j->start_row, j->stop_row, 1, NULL, NULL, j->journal);
+   else
+      j->rc = rt_replay_run_fragment(j->opt, j->parmsets, j->nparm, j->tdelta_ns, j->tstart_ns, j->nrows, j->row_base, j->W, j->bursts, j->nbursts, j->counts, j->events,
+                                     j->exact, j->exact_free, j->user, j->tap_path, NULL, NULL, j->stats, j->start_row, j->stop_row);
    clock_gettime(CLOCK_MONOTONIC, &b);
    *j->seconds = (double)(b.tv_sec - a.tv_sec) + 1e-9 * (double)(b.tv_nsec - a.tv_nsec);
    return NULL; }
-int rt_replay_run_fragments(const struct rt_options *opt, const struct rt_parms *parmsets, int nparm,
+static int run_fragments(const struct rt_options *opt, const struct rt_parms *parmsets, int nparm,
                   int64_t tdelta_ns, int64_t tstart_ns, int64_t nrows, int64_t row_base, const int *W,
                   const rtfe_burst *bursts, int64_t nbursts, const uint32_t *counts, const rtfe_event *events,
                   rt_exact_fn exact, rt_exact_free_fn exact_free, void *user,
-                  int nfrag, const char *const *tap_paths, const int64_t *start_rows, const int64_t *stop_rows, struct rt_replay_stats *stats, double *seconds) {
+                  int nfrag, const char *const *tap_paths, struct rt_journal *const *journals, const int64_t *start_rows, const int64_t *stop_rows,
+                  struct rt_replay_stats *stats, double *seconds) {
    if (nfrag < 1 || nfrag > 256) return -1;
    struct frag_job *jobs = (struct frag_job *)calloc((size_t)nfrag, sizeof *jobs);
    pthread_t *th = (pthread_t *)calloc((size_t)nfrag, sizeof *th);
    if (!jobs || !th) { free(jobs); free(th); return -1; }
    for (int i = 0; i < nfrag; ++i) {
       struct frag_job j = { opt, parmsets, nparm, tdelta_ns, tstart_ns, nrows, row_base, W, bursts, nbursts, counts, events, exact, exact_free, user,
-                            tap_paths[i], start_rows[i], stop_rows[i], &stats[i], &seconds[i], 0 };
+                            tap_paths ? tap_paths[i] : NULL, start_rows[i], stop_rows[i], stats ? &stats[i] : NULL, &seconds[i], 0, journals ? journals[i] : NULL };
       jobs[i] = j; }
    int started = 0, rc = 0;
    for (int i = 1; i < nfrag; ++i) { if (pthread_create(&th[i], NULL, frag_thread, &jobs[i]) != 0) break; started = i; }
@@ -537,6 +673,21 @@ int rt_replay_run_fragments(const struct rt_options *opt, const struct rt_parms 
    for (int i = 0; i < nfrag; ++i) if (jobs[i].rc != 0 && rc == 0) rc = jobs[i].rc;
    free(jobs); free(th);
    return rc; }
+int rt_replay_run_fragments(const struct rt_options *opt, const struct rt_parms *parmsets, int nparm,
+                  int64_t tdelta_ns, int64_t tstart_ns, int64_t nrows, int64_t row_base, const int *W,
+                  const rtfe_burst *bursts, int64_t nbursts, const uint32_t *counts, const rtfe_event *events,
+                  rt_exact_fn exact, rt_exact_free_fn exact_free, void *user,
+                  int nfrag, const char *const *tap_paths, const int64_t *start_rows, const int64_t *stop_rows, struct rt_replay_stats *stats, double *seconds) {
+   return run_fragments(opt, parmsets, nparm, tdelta_ns, tstart_ns, nrows, row_base, W, bursts, nbursts, counts, events, exact, exact_free, user,
+                        nfrag, tap_paths, NULL, start_rows, stop_rows, stats, seconds); }
+int rt_replay_journal_fragments(const struct rt_options *opt, const struct rt_parms *parmsets, int nparm,
+                  int64_t tdelta_ns, int64_t tstart_ns, int64_t nrows, int64_t row_base, const int *W,
+                  const rtfe_burst *bursts, int64_t nbursts, const uint32_t *counts, const rtfe_event *events,
+                  rt_exact_fn exact, rt_exact_free_fn exact_free, void *user,
+                  int nfrag, struct rt_journal *const *journals, const int64_t *start_rows, const int64_t *stop_rows, double *seconds) {
+   for (int i = 0; i < nfrag; ++i) if (!journals[i]) return -1;
+   return run_fragments(opt, parmsets, nparm, tdelta_ns, tstart_ns, nrows, row_base, W, bursts, nbursts, counts, events, exact, exact_free, user,
+                        nfrag, NULL, journals, start_rows, stop_rows, NULL, seconds); }
 
 struct read_job { int fd; char *dst; int64_t off, n; int rc; };
 static void *read_thread(void *p) {
@@ -572,7 +723,7 @@ int rt_replay_run_after_deskew(const struct rt_options *opt, const struct rt_par
                   rt_exact_fn exact, rt_exact_free_fn exact_free, void *user,
                   const char *tap_path, const char *log_path, const char *evt_path, struct rt_replay_stats *stats) {
    return replay_any(opt, parmsets, nparm, tdelta_ns, tstart_ns, nrows, row_base, W, bursts, nbursts, counts, events,
-                     exact, exact_free, user, tap_path, log_path, evt_path, stats, 1, NULL, 0, INT64_MAX, 0, NULL, NULL); }
+                     exact, exact_free, user, tap_path, log_path, evt_path, stats, 1, NULL, 0, INT64_MAX, 0, NULL, NULL, NULL); }
 
 int rt_replay_deskew(const struct rt_options *opt, const struct rt_parms *parmsets, int nparm,
                   int64_t tdelta_ns, int64_t tstart_ns, int64_t nrows, int64_t row_base, const int *W,
@@ -581,7 +732,7 @@ int rt_replay_deskew(const struct rt_options *opt, const struct rt_parms *parmse
                   const char *log_path, const char *evt_path, int append, int *delays, int *nblks, int *hit_end) {
    struct deskew_out o = { delays, nblks, hit_end, NULL, NULL };
    return replay_any(opt, parmsets, nparm, tdelta_ns, tstart_ns, nrows, row_base, W, bursts, nbursts, counts, events,
-                     exact, exact_free, user, NULL, log_path, evt_path, NULL, append, &o, 0, INT64_MAX, 0, NULL, NULL); }
+                     exact, exact_free, user, NULL, log_path, evt_path, NULL, append, &o, 0, INT64_MAX, 0, NULL, NULL, NULL); }
 
 
 int rt_replay_density(const struct rt_options *opt, const struct rt_parms *parmsets, int nparm,
@@ -591,7 +742,7 @@ int rt_replay_density(const struct rt_options *opt, const struct rt_parms *parms
                   const char *log_path, const char *evt_path, float *bpi, float *implied, int *nblks, int *hit_end) {
    struct deskew_out o = { NULL, nblks, hit_end, bpi, implied };
    return replay_any(opt, parmsets, nparm, tdelta_ns, tstart_ns, nrows, row_base, W, bursts, nbursts, counts, events,
-                     exact, exact_free, user, NULL, log_path, evt_path, NULL, 0, &o, 0, INT64_MAX, 0, NULL, NULL); }
+                     exact, exact_free, user, NULL, log_path, evt_path, NULL, 0, &o, 0, INT64_MAX, 0, NULL, NULL, NULL); }
 
 /* ... with the output files made by name as the reference makes them (<out_base>.tap with opt->tap_format, else the numbered
  * <out_base>.NNN.bin files, src/readtape.c:1091-1111) and the end-of-run summary (src/readtape.c:2021-2044) in the log */
@@ -601,7 +752,7 @@ int rt_replay_run_named(const struct rt_options *opt, const struct rt_parms *par
                   rt_exact_fn exact, rt_exact_free_fn exact_free, void *user,
                   const char *out_base, const char *in_name, const char *log_path, const char *evt_path, int append, struct rt_replay_stats *stats) {
    return replay_any(opt, parmsets, nparm, tdelta_ns, tstart_ns, nrows, row_base, W, bursts, nbursts, counts, events,
-                     exact, exact_free, user, NULL, log_path, evt_path, stats, append, NULL, 0, INT64_MAX, 0, out_base, in_name); }
+                     exact, exact_free, user, NULL, log_path, evt_path, stats, append, NULL, 0, INT64_MAX, 0, out_base, in_name, NULL); }
 
 /* ---------------------------------------------------------------------------------------------------------------------
  * Whirlwind: one chain per tape.  The device detector's state is handed from attempt to attempt (and from chunk to chunk of
@@ -786,3 +937,150 @@ int rt_replay_run_ww_detector(const struct rt_options *opt, const struct rt_parm
    free(rp.ww_state); free(rp.ww_events); free(rp.ww_counts);
    rt_dec_free(d);
    return (prepass_failed && !rp.device_failures && !rp.reference_fatal) ? -2 : 0; }
+
+/* ---------------------------------------------------------------------------------------------------------------------
+ * The finisher: ONE context for the whole tape.  It takes this thread's requests (rt_replay_set_text, rt_driver_set_run, rt_replay_set_peakstats) as the
+ * resident decode's run does, is given the fragments' journals in tape order, and ends with what ends a resident run: end_of_blocks, the summary, the
+ * peak statistics' report.  All its calls are made on the thread that made it.
+ * --------------------------------------------------------------------------------------------------------------------- */
+struct rt_finisher {
+   struct rt_dec *d; struct rt_textfile *text; struct rt_peakbins *bins;
+   int peaks, blklimit, limited, has_in; char in_name[1024];
+   int64_t lines_base, prev_final_abs, prev_end_counted, fragments; double wall0, seconds;
+   int all_ok; struct journal_work work; int64_t device_failures, reference_fatal, fatal_row, fatal_trk;
+   int32_t tried[RT_MAXPARMSETS], chosen[RT_MAXPARMSETS], goodmultiple; };
+
+static double mono_now(void) { struct timespec t; clock_gettime(CLOCK_MONOTONIC, &t); return (double)t.tv_sec + 1e-9 * (double)t.tv_nsec; }
+
+struct rt_finisher *rt_journal_finisher_new(const struct rt_options *opt, const struct rt_parms *parmsets, int nparm, int64_t tdelta_ns,
+                  const char *tap_path, const char *out_base, const char *in_name, const char *log_path, int append, struct rt_peakbins *bins) {
+   struct rt_finisher *f = (struct rt_finisher *)calloc(1, sizeof *f);
+   if (!f) return NULL;
+   struct rt_dec *d = rt_dec_new(opt, (float)tdelta_ns / 1e9f, tdelta_ns);
+   if (!d) { free(f); return NULL; }
+   f->d = d; f->bins = bins; f->all_ok = 1;
+   if (parmsets) {
+      memset(d->parmsets, 0, sizeof d->parmsets);
+      memcpy(d->parmsets, parmsets, sizeof(struct rt_parms) * (size_t)nparm); }
+   else for (int i = nparm; i < RT_MAXPARMSETS; ++i) d->parmsets[i].active = 0;
+   if (out_base) snprintf(d->outbase, sizeof d->outbase, "%s", out_base);
+   else if (tap_path) d->tapf = fopen(tap_path, "wb");
+   if (log_path) d->logf = fopen(log_path, append ? "a" : "w");
+   if (in_name) { snprintf(f->in_name, sizeof f->in_name, "%s", in_name); f->has_in = 1; }
+   f->wall0 = (double)time(NULL);
+   f->peaks = bins ? peak_attach(d) : 0;
+   f->text = text_attach(d);
+   f->blklimit = rt_driver_take_run(d, 0x7fffffff);
+   return f; }
+
+static void finisher_learn_bins(struct rt_finisher *f, float left, float bw) {
+   if (!f->d->peakstat.initialized) rt_peakstat_start(f->d, left, bw); }
+
+/* a fragment's histogram (as it was when the fragment ended, or at the record the block limit falls on) into the tape's: integer sums, in any order */
+static void finisher_add_peaks(struct rt_finisher *f, const struct rt_journal *j, const struct peak_counts *p) {
+   struct rt_dec *d = f->d;
+   struct rt_peakbins *B = f->bins;
+   if (!B || !(p->initialized || p->nraw > 0)) return;
+   int64_t nraw = p->nraw < j->raw_cap ? p->nraw : j->raw_cap;
+   pthread_mutex_lock(&B->mu);
+   if (!B->have && nraw > 0) { rt_peakstat_bins(d->opt.mode, j->raw[0].bitspacing, &B->leftbin, &B->binwidth); B->have = 1; }      /* (in tape order: the tape's first) */
+   const int have = B->have; const float left = B->leftbin, bw = B->binwidth;
+   pthread_mutex_unlock(&B->mu);
+   if (!have) return;
+   finisher_learn_bins(f, left, bw);
+   for (int64_t i = 0; i < nraw; ++i) if (j->raw[i].trk >= 0 && j->raw[i].trk < RT_MAXTRKS) rt_peakstat_count(d, j->raw[i].peaktime, j->raw[i].trk);
+   if (p->initialized)
+      for (int t = 0; t < RT_MAXTRKS; ++t) {
+         d->peakstat.trksums[t] += p->trksums[t];
+         for (int b = 0; b < RT_PEAKSTAT_BUCKETS; ++b) d->peakstat.counts[t][b] += p->counts[t][b]; } }
+
+/* The next fragment's journal, in tape order.  Returns 0, 1 once the block limit is reached (the journals behind it are not wanted), -1 for a journal
+ * that is not whole. */
+int rt_journal_finish(struct rt_finisher *f, struct rt_journal *j) {
+   if (!f || !j || !j->done || j->failed) return -1;
+   if (f->limited) return 1;
+   const double t0 = mono_now();
+   struct rt_dec *d = f->d;
+   /* lines_in ("samples were processed"): the fragment counted from its own start, the resident decode's attempt would have started where the fragment
+    * in front ended; and every fragment but the tape's last counted the + 1 of an end of the data */
+   const int64_t base = f->lines_base + (j->start_abs - f->prev_final_abs) - f->prev_end_counted;
+   size_t at = 0;
+   int rc = 0;
+   const struct peak_counts *limit_peak = NULL;
+   struct peak_counts snap;
+   struct jrec r;
+   if (d->numblks >= f->blklimit) { f->limited = 1; rc = 1; }      /* (a limit of 0) */
+   while (!rc && at < j->len) {
+      if (j->len - at < sizeof r) { rc = -1; break; }
+      memcpy(&r, j->buf + at, sizeof r); at += sizeof r;
+      const size_t words = (size_t)(r.ndata < 0 ? 0 : r.ndata) + (size_t)(r.nfaked < 0 ? 0 : r.nfaked);
+      if (r.magic != JREC_MAGIC || r.ndata < 0 || r.ndata > RT_MAXBLOCK || (r.nfaked != 0 && r.nfaked != r.ndata) || r.parmset < 0 || r.parmset >= RT_MAXPARMSETS
+          || j->len - at < words * sizeof(uint16_t) + (r.has_snap ? sizeof snap : 0)) { rc = -1; break; }
+      memcpy(d->data, j->buf + at, sizeof(uint16_t) * (size_t)r.ndata); at += sizeof(uint16_t) * (size_t)r.ndata;
+      if (r.nfaked) { memcpy(d->data_faked, j->buf + at, sizeof(uint16_t) * (size_t)r.nfaked); at += sizeof(uint16_t) * (size_t)r.nfaked; }
+      if (r.has_snap) { memcpy(&snap, j->buf + at, sizeof snap); at += sizeof snap; }
+      d->parmset = r.parmset; d->tries = r.tries; d->results[r.parmset] = r.res;
+      d->timenow = r.timenow; d->t_blockstart = r.t_blockstart;
+      d->lines_in = base + r.lines_in;
+      d->numblks_goodmultiple = f->goodmultiple + r.goodmultiple;
+      for (int i = 0; i < RT_MAXPARMSETS; ++i) { d->parmsets[i].tried = f->tried[i] + r.tried[i]; d->parmsets[i].chosen = f->chosen[i] + r.chosen[i]; }
+      switch ((enum rt_bstate)r.blktype) {
+      case RT_BS_TAPEMARK: rt_got_tapemark(d); break;
+      case RT_BS_BLOCK:    rt_got_datablock(d, 0); break;
+      case RT_BS_BADBLOCK: rt_got_datablock(d, 1); break;
+      default: rc = -1; break; }
+      if (!rc && d->numblks >= f->blklimit) {                    /* as rt_process_blocks' loop ends: behind the block that reaches the limit */
+         f->limited = 1; rc = 1;
+         f->all_ok = f->all_ok && r.all_clean;
+         f->work.attempts += r.work.attempts; f->work.exact_scans += r.work.exact_scans; f->work.chained += r.work.chained;
+         f->work.events_delivered += r.work.events_delivered; f->work.agc_mismatches += r.work.agc_mismatches;
+         if (r.has_snap) limit_peak = &snap; } }
+   if (rc == 0) {                                               /* the whole fragment */
+      d->timenow = j->timenow;
+      d->lines_in = base + j->lines_in;
+      f->lines_base = d->lines_in; f->prev_final_abs = j->final_abs; f->prev_end_counted = j->end_counted;
+      f->goodmultiple += j->goodmultiple; d->numblks_goodmultiple = f->goodmultiple;
+      for (int i = 0; i < RT_MAXPARMSETS; ++i) { f->tried[i] += j->tried[i]; f->chosen[i] += j->chosen[i]; d->parmsets[i].tried = f->tried[i]; d->parmsets[i].chosen = f->chosen[i]; }
+      f->all_ok = f->all_ok && j->all_clean;
+      /* the replay's own counters are the work the fragments did (each closes with an attempt that finds nothing, each starts on a zone's first row) */
+      f->work.attempts += j->stats.attempts; f->work.exact_scans += j->stats.exact_scans;
+      f->work.chained += j->stats.chained;
+      f->work.events_delivered += j->stats.events_delivered; f->work.agc_mismatches += j->stats.agc_mismatches;
+      finisher_add_peaks(f, j, &j->peak); }
+   else if (rc == 1 && limit_peak) finisher_add_peaks(f, j, limit_peak);
+   if (rc >= 0) {
+      f->device_failures += j->stats.device_failures;
+      if (j->stats.reference_fatal && !f->reference_fatal) { f->reference_fatal = j->stats.reference_fatal; f->fatal_row = j->stats.fatal_row; f->fatal_trk = j->stats.fatal_trk; }
+      ++f->fragments; }
+   f->seconds += mono_now() - t0;
+   return rc; }
+
+/* What ends a run: the end of the output file(s), the summary, the statistics' report.  Fills *stats as a resident replay would (the replay's own counters
+ * are the fragments' sums), *seconds = the time spent in rt_journal_finish and here.  Frees the finisher. */
+int rt_journal_finisher_end(struct rt_finisher *f, struct rt_replay_stats *stats, double *seconds) {
+   if (!f) return -1;
+   const double t0 = mono_now();
+   struct rt_dec *d = f->d;
+   if (!f->limited) d->lines_in = f->lines_base;
+   rt_end_of_blocks(d, f->blklimit);
+   if (f->text) { d->text = NULL; d->text_record = NULL; d->text_tapemark = NULL; rt_text_close(f->text, 1); }
+   if (f->has_in) rt_write_summary(d, f->in_name, difftime(time(NULL), (time_t)f->wall0));
+   if (f->peaks) {
+      if (f->bins && !d->peakstat.initialized) {                /* (no transition anywhere: the report is the resident decode's of an untouched histogram) */
+         memset(&d->peakstat, 0, sizeof d->peakstat); }
+      peak_report(d); }
+   if (stats) {
+      memset(stats, 0, sizeof *stats);
+      stats->attempts = f->work.attempts; stats->exact_scans = f->work.exact_scans; stats->chained = f->work.chained;
+      stats->events_delivered = f->work.events_delivered; stats->agc_mismatches = f->work.agc_mismatches;
+      stats->blocks = d->numblks; stats->tapemarks = d->numtapemarks; stats->blocks_with_errors = d->numblks_err;
+      stats->blocks_with_warnings = d->numblks_warn; stats->blocks_unusable = d->numblks_unusable; stats->all_ok = f->all_ok;
+      stats->data_bytes = d->numdatabytes; stats->device_failures = f->device_failures;
+      stats->reference_fatal = f->reference_fatal; stats->fatal_row = f->fatal_row; stats->fatal_trk = f->fatal_trk; }
+   if (d->tapf) fclose(d->tapf);
+   if (d->logf) fclose(d->logf);
+   f->seconds += mono_now() - t0;
+   if (seconds) *seconds = f->seconds;
+   rt_dec_free(d);
+   free(f);
+   return 0; }

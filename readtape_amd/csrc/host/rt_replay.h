@@ -35,6 +35,7 @@ struct rt_replay {
    rt_exact_fn exact; rt_exact_free_fn exact_free; void *exact_user;
    int64_t pos, saved_pos, cur_row; double saved_time;
    int64_t stop_row;                   /* fragment decode: no attempt starts at or behind this row */
+   int     end_counted;                /* ... a first attempt found the end: lines_in has its + 1 */
    /* Whirlwind */
    rt_ww_scan_fn ww_scan; void *ww_user;
    unsigned char *ww_state, *ww_chunk_state, *ww_chunk_end;   /* ntrks tracks of ww_track_bytes each: at the attempt's start / at the chunk's first row / behind the chunk */
@@ -133,6 +134,42 @@ void rt_replay_set_text(const rt_text_options *o, const char *base, const char *
  * trksums[RT_MAXTRKS]) and skew_compute_deskew's answer, of the last such decode on this thread; 0 if there is none. */
 void rt_replay_set_peakstats(const char *base, int quiet, int deskew);
 int  rt_replay_get_peakstats(int which, float *leftbin, float *binwidth, int32_t *counts, int32_t *trksums, int *ok, float *peak_frac, float *stddev_frac);
+
+/* ---- the windowed decode: fragments journal their blocks, ONE finisher puts them out ----
+ * A journal holds what a fragment's replay would have put out - per block the type, the data words, the chosen attempt's results, tries and parameter
+ * set, the times, the row behind it, and the running counters of the summary - in memory, in a private format.  rt_replay_journal_fragments is
+ * rt_replay_run_fragments in journal mode: journals[i] takes fragment i's blocks, nothing is written.
+ * Peak statistics: journals made with an rt_peakbins record into their own histogram on the bins the tape's first transition fixes; `first` marks the tape's
+ * first fragment, which publishes them; a fragment that does not know them yet keeps its transitions for the finisher (nobody waits, so any order and
+ * any number of threads will do).  snapshots: every record carries the histogram so far (wanted with a block limit: the finisher stops inside a journal). */
+struct rt_journal;
+struct rt_peakbins;
+struct rt_finisher;
+struct rt_peakbins *rt_peakbins_new(void);
+void rt_peakbins_free(struct rt_peakbins *b);
+struct rt_journal *rt_journal_new(struct rt_peakbins *bins, int first, int snapshots);
+void    rt_journal_free(struct rt_journal *j);
+int64_t rt_journal_bytes(const struct rt_journal *j);
+int     rt_journal_records(const struct rt_journal *j);
+int     rt_journal_stats(const struct rt_journal *j, struct rt_replay_stats *stats);      /* the fragment's own replay statistics (-1: not run) */
+int64_t rt_journal_final_row(const struct rt_journal *j);      /* the absolute row at which the fragment's last attempt ended (-1: not run) */
+/* one block of a context into a journal, as the fragment replay does it (blktype: RT_BS_TAPEMARK, _BLOCK or _BADBLOCK; d->parmset names the results) */
+void    rt_journal_record(struct rt_journal *j, struct rt_dec *d, int blktype);
+void    rt_journal_close(struct rt_journal *j);                /* ... and the end of such a journal: it is whole */
+int rt_replay_journal_fragments(const struct rt_options *opt, const struct rt_parms *parmsets, int nparm,
+                  int64_t tdelta_ns, int64_t tstart_ns, int64_t nrows, int64_t row_base, const int *W,
+                  const rtfe_burst *bursts, int64_t nbursts, const uint32_t *counts, const rtfe_event *events,
+                  rt_exact_fn exact, rt_exact_free_fn exact_free, void *user,
+                  int nfrag, struct rt_journal *const *journals, const int64_t *start_rows, const int64_t *stop_rows, double *seconds);
+/* The finisher is one decoder context around the output stage of the resident decode: it takes the calling thread's requests (rt_replay_set_text,
+ * rt_driver_set_run, and with `bins` rt_replay_set_peakstats), names its files as rt_replay_run_named (out_base) or rt_replay_run (tap_path) does, and
+ * appends to the log a pre-pass began (append).  rt_journal_finish: the next fragment's journal, in tape order, whole fragments only (0; 1: the block
+ * limit is reached, nothing more is wanted; -1: not a finished journal).  rt_journal_finisher_end: the end of the files, the summary (with in_name), the
+ * statistics' report; *stats as a resident replay's, *seconds the finisher's own time; the finisher is gone.  One thread makes all these calls. */
+struct rt_finisher *rt_journal_finisher_new(const struct rt_options *opt, const struct rt_parms *parmsets, int nparm, int64_t tdelta_ns,
+                  const char *tap_path, const char *out_base, const char *in_name, const char *log_path, int append, struct rt_peakbins *bins);
+int rt_journal_finish(struct rt_finisher *f, struct rt_journal *j);
+int rt_journal_finisher_end(struct rt_finisher *f, struct rt_replay_stats *stats, double *seconds);
 
 #ifdef __cplusplus
 }

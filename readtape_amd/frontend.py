@@ -373,6 +373,12 @@ class ScanResult:
         self.fetch_times = tt                              # (wait for the scan, the tables, the events)
         return self
 
+    def detach(self):
+        """The fetched event lists as the result's own copy: the context's next scan may reuse the buffer they were read from.  -> self"""
+        if self._events is not None:
+            self._events = np.array(self._events)
+        return self
+
     @property
     def nbursts(self):
         return len(self.bursts)

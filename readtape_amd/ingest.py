@@ -54,7 +54,7 @@ def _prepass_needs(hdr, cfgkw, deskew):
     return need_bpi, need_skew
 
 
-def _settle(hdr, full, opts, cfgkw, need_bpi, need_skew, make_fe, run):
+def _settle(hdr, full, opts, cfgkw, need_bpi, need_skew, make_fe, run, log_path=None):
     """The two pre-passes in the reference's order (src/readtape.c:1656-1717): the density, then the delays with that density -> cfgkw with "bpi" / "skew".
     run(what, fn): calls fn(rows, more_rows) on the rows the caller has - the streaming reader's growing prefix, a rank's resident share - and returns
     its answer (never None: an undecided pre-pass is the caller's to resolve or to refuse)."""
@@ -68,17 +68,17 @@ def _settle(hdr, full, opts, cfgkw, need_bpi, need_skew, make_fe, run):
     cfgkw = dict(cfgkw)
     if need_bpi:
         cfgkw["bpi"] = run("density detection", lambda rows, more: pipeline.detect_density(
-            hdr, rows, full, options(0.0), make_fe, invert=invert, first_prefix_rows=max(1, int(rows.shape[0])), more_rows=more))
+            hdr, rows, full, options(0.0), make_fe, invert=invert, first_prefix_rows=max(1, int(rows.shape[0])), more_rows=more, log_path=log_path))
     if need_skew:
         rest = {k: v for k, v in cfgkw.items() if k not in ("invert", "find_zeros", "differentiate", "skew")}
         bpi = frontend.FrontEndConfig.from_header(hdr, **({"bpi": cfgkw["bpi"]} if "bpi" in cfgkw else {})).bpi
         cfgkw["skew"] = run("-deskew calibration", lambda rows, more: pipeline.calibrate_deskew(
             hdr, rows, full, options(bpi), make_fe, invert=invert, find_zeros=find_zeros, differentiate=differentiate,
-            first_prefix_rows=max(1, int(rows.shape[0])), more_rows=more, **rest))
+            first_prefix_rows=max(1, int(rows.shape[0])), more_rows=more, log_path=log_path, append=bool(need_bpi and log_path), **rest))
     return cfgkw
 
 
-def _prepasses(hdr, fd, off, nrows, nth, full, opts, cfgkw, deskew, prepass_rows, device, fe_factory=None, backend=None, lib=None):
+def _prepasses(hdr, fd, off, nrows, nth, full, opts, cfgkw, deskew, prepass_rows, device, fe_factory=None, backend=None, lib=None, log_path=None):
     """What the reference settles before its main pass (src/readtape.c:1656-1717), on a prefix of the file: the density of a header without one, then the
     -deskew delays with that density - pipeline.detect_density / calibrate_deskew, which the resident decode runs on its whole tape.  -> cfgkw with what they
     found ("bpi", "skew"); unchanged, and nothing read or launched, where neither is asked for.  off: the payload behind the skipped rows; nrows: used rows.
@@ -123,7 +123,7 @@ def _prepasses(hdr, fd, off, nrows, nth, full, opts, cfgkw, deskew, prepass_rows
             del rows
             want = min(nrows, want * 4)                    # (None only with more rows behind the prefix: want < nrows)
 
-    return _settle(hdr, full, opts, cfgkw, need_bpi, need_skew, make_fe, run)
+    return _settle(hdr, full, opts, cfgkw, need_bpi, need_skew, make_fe, run, log_path=log_path)
 
 
 def plan_windows(raw_rows, window_rows, halo_rows, subsample=1, skip=0, ramp=True):
@@ -183,13 +183,62 @@ def decode_file_streaming(path, tap_path, window_rows=1 << 24, halo_rows=1 << 17
     invert / find_zeros / differentiate and no delays.  A pre-pass whose stopping rule is not met inside the prefix gets a prefix four times as long, up
     to the whole tape; if that does not fit the device a RuntimeError says so (nothing is ever streamed with a guessed density or partial delays).
     statistics["bpi"], ["skew"]: what the scans ran with.  With the defaults and a header that states its density nothing of this costs a launch or a buffer."""
+    pipeline.refuse_peakstats(peakstats, "ingest.decode_file_streaming")
+    return _decode_file(path, tap_path, window_rows, halo_rows, opts, cfgkw, device, replay_threads, read_threads, replay_split, scan_contexts, ramp,
+                        subsample, skip, deskew, skew, prepass_rows, None)
+
+
+class _Windows:
+    """What decode_file_windows adds to the streaming reader: the header as the command line overrides it, the parameter sets of a .parms text, the log the
+    pre-passes begin, and the finisher (pipeline.Finisher) the windows' journals go to - made on the caller's thread once the configuration is settled."""
+
+    def __init__(self, out, hdr_overrides, parms_text):
+        self.out, self.parms_text = out, parms_text
+        self.hdr_overrides = {{"order": "trkorder"}.get(k, k): v for k, v in (hdr_overrides or {}).items() if v is not None}
+        self.log_path = out.get("log_path")
+
+    def header(self, hdr):
+        import dataclasses
+        return dataclasses.replace(hdr, **self.hdr_overrides) if self.hdr_overrides else hdr
+
+    def parmsets(self, hdr, opts):
+        nsets = opts.nparmsets or (15 if opts.multiple_tries else 1)
+        if not self.parms_text:
+            return pipeline.default_parmsets(hdr.mode, nsets)
+        arr = (pipeline._Parms * 15)()
+        n = pipeline._load_decode_lib().rt_parse_parms_text(hdr.mode, self.parms_text.encode(), arr)
+        if n <= 0:
+            raise ValueError("bad .parms text")
+        return [arr[i] for i in range(n)][:nsets]
+
+    def finisher(self, hdr, cfg, full, opts, began):
+        return pipeline.Finisher(hdr, cfg, full, opts, append=began, **self.out)
+
+
+class _Consumed:
+    """A device window of the windowed decode stays as it is until the finisher has taken its journals (a fragment whose neighbour's last block ran into it is
+    replayed again, from the window's rows): what launch() waits for besides the window's replays."""
+
+    def __init__(self, waited):
+        self.ev, self.waited = threading.Event(), waited
+
+    def result(self):
+        t0 = time.perf_counter()
+        self.ev.wait()
+        self.waited[0] += time.perf_counter() - t0
+
+
+def _decode_file(path, tap_path, window_rows, halo_rows, opts, cfgkw, device, replay_threads, read_threads, replay_split, scan_contexts, ramp,
+                 subsample, skip, deskew, skew, prepass_rows, sink):
+    """decode_file_streaming's pipeline; sink: None, or decode_file_windows' _Windows - the fragments journal their blocks and one finisher puts them out."""
     import queue
     import torch
-    pipeline.refuse_peakstats(peakstats, "ingest.decode_file_streaming")
     assert window_rows % 1024 == 0
     t_enter = time.perf_counter()
     opts = opts or pipeline.DecodeOptions()
     hdr, off, raw_rows = _payload_geometry(path)
+    if sink:
+        hdr = sink.header(hdr)
     if hdr.mode == tbin.MODE_WW:
         raise NotImplementedError("Whirlwind tapes are one chain (no independent fragments): read the file and use pipeline.decode_tape_ww")
     nth, skip = int(subsample), int(skip)
@@ -203,18 +252,20 @@ def decode_file_streaming(path, tap_path, window_rows=1 << 24, halo_rows=1 << 17
     gpu_mark = os.environ.get("RTFE_PACK_EVENTS") != "0" and not os.environ.get("RT_INGEST_HOST_MARK")
     if nth > 1 and not gpu_mark:
         raise NotImplementedError("subsample > 1: the windows' end-of-data check is the thinning kernel's (unset RT_INGEST_HOST_MARK / RTFE_PACK_EVENTS=0)")
-    full = pipeline.default_parmsets(hdr.mode, opts.nparmsets or (15 if opts.multiple_tries else 1))
+    full = sink.parmsets(hdr, opts) if sink else pipeline.default_parmsets(hdr.mode, opts.nparmsets or (15 if opts.multiple_tries else 1))
     dev = torch.device(device)
     cfgkw = dict(cfgkw or {})
     if skew is not None:
         cfgkw["skew"] = [int(x) for x in skew]
     fd = os.open(path, os.O_RDONLY)
+    finisher = None
     try:
-        cfgkw = _prepasses(hdr, fd, off, nrows, nth, full, opts, cfgkw, deskew, int(prepass_rows), device)
+        began = bool(sink and sink.log_path and nrows > 0 and any(_prepass_needs(hdr, cfgkw, deskew)))      # (the pre-passes begin the log, the finisher continues it)
+        cfgkw = _prepasses(hdr, fd, off, nrows, nth, full, opts, cfgkw, deskew, int(prepass_rows), device, log_path=sink.log_path if sink else None)
+        cfg = frontend.FrontEndConfig.from_header(hdr, parmsets=pipeline.frontend_parmsets(full), **cfgkw)
     except BaseException:
         os.close(fd)
         raise
-    cfg = frontend.FrontEndConfig.from_header(hdr, parmsets=pipeline.frontend_parmsets(full), **cfgkw)
     nctx = max(2, int(scan_contexts))
     fes = [frontend.FrontEnd(cfg, device=device) for _ in range(nctx)]      # window k is fetched while k + 1 .. are copied and scanned
     fe = fes[0]
@@ -352,6 +403,7 @@ def decode_file_streaming(path, tap_path, window_rows=1 << 24, halo_rows=1 << 17
                 if k >= NP:
                     copied[k % NP].synchronize()           # the pinned buffer's last copy (window k - NP) has left it
                 end = read_window(k)
+                stats["windows_read"] = k + 1
                 if stop.is_set():
                     break
                 item = launch(k, end)
@@ -369,6 +421,15 @@ def decode_file_streaming(path, tap_path, window_rows=1 << 24, halo_rows=1 << 17
     retired = []                                          # scan contexts replaced by ones with a calibrated screen floor (closed at the end: a scan of theirs may still be in flight)
     floor_state = {"tries": 2, "floor": None}
     pieces = []                                           # per window: bytes, or the future that returns (bytes, replay stats, seconds)
+
+    def journal_window(k, res, piece, lo, starts, stops, safes):
+        """the windowed decode's replay of a window: its sub-fragments into journals -> what the finisher needs to take them (and to replay one again)"""
+        t0 = time.perf_counter()
+        js = [finisher.journal(first=(lo == 0 and j == 0)) for j in range(len(starts))]
+        live.update(js)
+        secs = pipeline.journal_fragments(hdr, cfg, fe_exact, res, piece, lo, starts, stops, js, full, opts, exact_lock=exact_lock)
+        mark("replay", k, t0)
+        return dict(k=k, journals=js, secs=secs, starts=starts, stops=stops, safes=safes, res=res, piece=piece, lo=lo)
 
     def replay(k, res, piece, lo, bound, start=None, tag=""):
         t0 = time.perf_counter()
@@ -413,6 +474,9 @@ def decode_file_streaming(path, tap_path, window_rows=1 << 24, halo_rows=1 << 17
     total = 0
     calib_lock = threading.Lock()
     marks_seen = [threading.Event() for _ in spans]
+    fin_wait = [0.0]
+    consumed = [_Consumed(fin_wait) for _ in spans] if sink else None
+    live = set()                                          # journals made and not yet finished or dropped
     fetchers = ThreadPoolExecutor(nctx)                    # a window's results are fetched (and its replays queued) beside its neighbours': a fetch is ~6 ms of host-side work
     fetch_streams = [torch.cuda.Stream(dev) for _ in range(nctx)]
     wait_s = [0.0]
@@ -503,8 +567,16 @@ def decode_file_streaming(path, tap_path, window_rows=1 << 24, halo_rows=1 << 17
                     first = 0 if lo == 0 else int(res.bursts[0]["zone_first"])
                     starts, stops = [first] + cuts, cuts + [bound]
                     keep = [j for j in range(nsub) if stops[j] is None or stops[j] > starts[j]]
-                    out = [pool.submit(replay_window, k, res, piece, lo, [starts[j] for j in keep], [stops[j] for j in keep])]
-                    busy[k % depth] = _All(out)
+                    if sink:
+                        safes = [int(res.bursts[(res.nbursts * j) // nsub]["safe_last"]) for j in range(nsub)]
+                        out = [pool.submit(journal_window, k, res, piece, lo, [starts[j] for j in keep], [stops[j] for j in keep], [safes[j] for j in keep])]
+                        busy[k % depth] = _All(out + [consumed[k]])
+                    else:
+                        out = [pool.submit(replay_window, k, res, piece, lo, [starts[j] for j in keep], [stops[j] for j in keep])]
+                        busy[k % depth] = _All(out)
+                elif sink:
+                    out = [journal_window(k, res, piece, lo, [0 if lo == 0 else int(res.bursts[0]["zone_first"])], [bound], [int(res.bursts[0]["safe_last"])])]
+                    busy[k % depth] = consumed[k]
                 else:
                     out = [replay(k, res, piece, lo, bound)]
         finally:
@@ -521,9 +593,13 @@ def decode_file_streaming(path, tap_path, window_rows=1 << 24, halo_rows=1 << 17
         gc.disable()                                      # a full collection walks every object of the process (PyTorch is loaded: tens of ms) with the interpreter lock held - every stage stalls at once
     sys.setswitchinterval(float(os.environ.get("RT_INGEST_SWITCH", "0.0002")))      # a dozen threads hand the interpreter lock around between system calls: at the default 5 ms a stage waits longer for the lock than it works
     try:
-        with open(tap_path, "wb") as tapf:
+        import contextlib
+        with (contextlib.nullcontext() if sink else open(tap_path, "wb")) as tapf:      # (the windowed decode's files are the finisher's)
             # software pipeline: the producer thread reads window after window and queues each one's copy and scan on the device; the fetchers bring
             # the windows' results to the host and hand them to the replay threads; this thread collects the pieces in window order
+            if sink:                                          # (on this thread, which makes all its calls; the `finally` below ends it if anything fails)
+                finisher = sink.finisher(hdr, cfg, full, opts, began)
+                stats.update(bursts=0, fragment_work={k: 0 for k in pipeline.WORK_COUNTERS})
             prod.start()
             while True:
                 k, fut = launched.get()
@@ -531,8 +607,40 @@ def decode_file_streaming(path, tap_path, window_rows=1 << 24, halo_rows=1 << 17
                     if isinstance(fut, BaseException):
                         raise fut
                     break
-                if fut is not None:
+                if fut is not None and finisher:
+                    # the windowed decode: this thread is the finisher's - a window's journals are taken as soon as every window in front has been
+                    for pc in fut.result():
+                        got = pc.result() if hasattr(pc, "result") else pc
+                        for j, jr in enumerate(got["journals"]):
+                            live.discard(jr)
+                            if finisher.limited:
+                                finisher.discard(jr)
+                                continue
+                            if (got["lo"] > 0 or j > 0) and finisher.overrun(got["lo"] + got["safes"][j]):
+                                # the block in front ended inside this fragment's first zone, past the proven restart: again, from there (pipeline.Finisher.overrun)
+                                finisher.discard(jr)
+                                jr = finisher.journal(first=False)
+                                got["secs"][j] += pipeline.journal_fragments(hdr, cfg, fe_exact, got["res"], got["piece"], got["lo"], [finisher.final_row - got["lo"]],
+                                                                             [got["stops"][j]], [jr], full, opts, exact_lock=exact_lock)[0]
+                                stats["fragments_redone"] = stats.get("fragments_redone", 0) + 1
+                            t_replay += got["secs"][j]
+                            work = finisher.finish(jr)[2]
+                            for key in work:
+                                stats["fragment_work"][key] += work[key]
+                            stats["fragments"] = stats.get("fragments", 0) + 1
+                        stats["bursts"] += got["res"].nbursts
+                        consumed[got["k"]].ev.set()
+                    if finisher.limited:
+                        stop.set()                                # (the block limit is reached: nothing more is read)
+                        for ev in consumed:
+                            ev.ev.set()
+                elif fut is not None:
                     pieces.extend(fut.result())
+            if finisher:
+                f2, finisher = finisher, None
+                fst = f2.end()
+                total = int(fst["data_bytes"])
+                stats.update(fst)
             for pc in pieces:                                 # in window order
                 got = pc.result() if hasattr(pc, "result") else [pc]
                 for data, st, secs in got:
@@ -542,7 +650,7 @@ def decode_file_streaming(path, tap_path, window_rows=1 << 24, halo_rows=1 << 17
                     for key in ("blocks", "tapemarks", "events_delivered", "exact_scans"):
                         stats[key] += int(st[key])
                     stats["all_ok"] = bool(stats["all_ok"] and st["all_ok"])      # (every fragment's blocks were clean: the reference's "ok")
-            if total > 0:
+            if total > 0 and not sink:
                 tapf.write(b"\xff\xff\xff\xff")                   # src/readtape.c:1885
         torch.cuda.synchronize(dev)
         dt = time.perf_counter() - t_start
@@ -551,6 +659,8 @@ def decode_file_streaming(path, tap_path, window_rows=1 << 24, halo_rows=1 << 17
         if gc_was:
             gc.enable()
         stop.set()
+        for ev in consumed or ():                         # (... or for a window the finisher will not take any more)
+            ev.ev.set()
         for sem in ctx_free:                              # (a producer waiting for a context wakes up and sees the stop flag)
             sem.release()
         if prod.is_alive():
@@ -561,10 +671,16 @@ def decode_file_streaming(path, tap_path, window_rows=1 << 24, halo_rows=1 << 17
         os.close(fd)
         if pool:
             pool.shutdown(wait=True, cancel_futures=True)
+        if finisher is not None:                          # (a run that ended early; no fragment is running any more: the files are closed, the requests taken back)
+            finisher.abandon()
+        for jr in live:                                   # (journals of windows nobody collected)
+            pipeline._load_decode_lib().rt_journal_free(jr)
         torch.cuda.synchronize(dev)
         fe_exact.close()
         for f in list(fes) + retired:
             f.close()
+    if sink:
+        stats["finisher_wait_seconds"] = fin_wait[0]
     if trace is not None:
         for k in range(len(spans)):                       # the device's own clock: a window's copy and the end of its scan, ms behind the start of the timed region
             if ("copy0", k) in gpu_ev:
@@ -572,6 +688,33 @@ def decode_file_streaming(path, tap_path, window_rows=1 << 24, halo_rows=1 << 17
                 trace.append(("gpu_copy", k, c0 / 1e3, c1 / 1e3)); trace.append(("gpu_scan_done", k, c1 / 1e3, s1 / 1e3))
         stats["trace"] = sorted(trace, key=lambda x: x[2])
     stats.update(setup_seconds=t_start - t_enter, rows=data_end[0], seconds=dt, msamples_per_s=data_end[0] / dt / 1e6, replay_seconds=t_replay, read_seconds=t_read[0], scan_wait_seconds=wait_s[0],
-                 replay_events_per_s=(stats["events_delivered"] / t_replay) if t_replay > 0 else None, tap_bytes=total + (4 if total else 0), screen_floor_height=floor_state["floor"],
+                 replay_events_per_s=(stats["events_delivered"] / t_replay) if t_replay > 0 else None, tap_bytes=(total + (4 if total else 0)) if not sink else None, screen_floor_height=floor_state["floor"],
                  raw_rows=skip + data_end[0] * nth, bpi=cfg.bpi, skew=list(cfg.skew) if cfg.skew is not None else None)
     return stats
+
+
+def decode_file_windows(path, out_base=None, tap_path=None, log_path=None, tap_format=True, labels=False, blklimit=None, textfile=None, created=None,
+                        peakstats=False, quiet=False, hdr_overrides=None, in_name=None, parms_text=None, window_rows=1 << 24, halo_rows=1 << 17,
+                        opts: pipeline.DecodeOptions | None = None, cfgkw=None, device="cuda:0", replay_threads: int = 1, read_threads: int = 4, replay_split: int = 1,
+                        scan_contexts: int = 3, ramp: bool = True, subsample: int = 1, skip: int = 0, deskew: bool = False, skew=None, prepass_rows: int = 1 << 22):
+    """decode_file_streaming's pipeline with the resident decode's outputs (pipeline.decode_tape's): the .tbin file `path` goes through the same reads, pinned
+    buffers, streams, scan contexts, windows, halos and replay threads (window_rows ... prepass_rows: as there), but the windows' fragments write no pieces of a
+    .tap - each journals its blocks (pipeline.journal_fragments) - and ONE finisher, on the caller's thread, takes a window's journals as soon as every window in
+    front of it is done and puts the blocks out in tape order: out_base's files by the reference's names (<out_base>.tap, or with tap_format=False the numbered
+    and label-named .bin files) or the one file tap_path, the log with its per-block lines and its summary (log_path; in_name, default `path`), the text file
+    (textfile, created), labels, blklimit, peakstats / quiet exactly as decode_tape's arguments of those names.  With blklimit reached nothing more is read.
+    hdr_overrides: what the command line sets over the header before anything is planned - order (or trkorder), bpi, ips, mode, ntrks; parms_text: a .parms text.
+    The pre-passes (density, deskew) begin the log, and with peakstats the deskew pre-pass writes <base>.peakstats_deskew.csv, as in the resident decode.
+    Returns decode_file_streaming's statistics with the resident decode's (blocks, tapemarks, data_bytes, all_ok ..., peakstats / skew_ok) in place of the sums,
+    and bursts (the windows' own, summed), fragment_work (the fragments' replay counters, summed: what attempts, exact_scans ... are made of), windows_read, fragments, finisher_seconds (the finisher's own time) and finisher_wait_seconds (what the pipeline waited for it to release a window)."""
+    lib = pipeline._load_decode_lib()
+    if out_base is None and tap_path is None:
+        raise ValueError("decode_file_windows: give out_base or tap_path")
+    out = dict(tap_path=tap_path, log_path=log_path, out_base=out_base, in_name=(in_name or path) if out_base else None, tap_format=tap_format, labels=labels,
+               blklimit=blklimit, textfile=textfile, created=created, quiet=quiet)
+    out["peak_base"] = pipeline._request_peakstats(lib, peakstats, out_base, tap_path, quiet, bool(deskew) or skew is not None)
+    try:
+        return _decode_file(path, tap_path or out_base + ".tap", window_rows, halo_rows, opts, cfgkw, device, replay_threads, read_threads, replay_split, scan_contexts,
+                            ramp, subsample, skip, deskew, skew, prepass_rows, _Windows(out, hdr_overrides, parms_text))
+    finally:
+        lib.rt_replay_set_peakstats(None, 0, 0)

@@ -133,7 +133,9 @@ def _exact_callbacks(fe, rows, ntrks, fe_factory=None, lock=None):
                 return 1
             cap = int(B["event_cap"])
             base = int(B["event_base"]) + parmset * ntrks * cap
-            ev = np.ascontiguousarray(ex._events[base: base + ntrks * cap])
+            ev = ex._events[base: base + ntrks * cap]
+            # (a shared handle - a lock is given -: a copy, the replay reads the lists after the lock is released, when the next rescan may fill the context's buffer)
+            ev = np.array(ev) if lock is not None else np.ascontiguousarray(ev)
             C.memmove(burst_out, B.tobytes(), frontend.BURST_DTYPE.itemsize)
             for t in range(ntrks):
                 counts_out[t] = int(ex.counts[0, parmset, t])
@@ -627,6 +629,28 @@ def decode_fragments(hdr, cfg, fe, res, rows_with_halo, lo, start_rows, stop_row
     return out
 
 
+def scan_spans(fe, rows, spans, halo_rows):
+    """The fragments `spans` of a resident tape, scanned one after the other on `fe`, each with a halo that grows until it holds the zone behind the
+    fragment's last own burst -> (k, lo, hi, rows with halo, scan result, start row, stop row or None) of every fragment that owns a burst."""
+    n = int(rows.shape[0])
+    for k, (lo, hi) in enumerate(spans):
+        if hi <= lo:
+            continue
+        is_last = hi >= n
+        halo = halo_rows
+        while True:
+            end = n if is_last else min(n, hi + halo)
+            piece = rows[lo:end]
+            res, nb, bound = scan_fragment(fe, piece, hi - lo, lo, lo == 0, is_last)()
+            if nb is not None or end >= n:
+                break
+            halo *= 4                                   # the last own burst runs past the halo: ask the neighbour for more
+        # (nb None with the halo at the end of the tape: no further zone exists, the last own burst runs to the end of the data)
+        if res.nbursts == 0:
+            continue
+        yield k, lo, hi, piece, res, (0 if lo == 0 else int(res.bursts[0]["zone_first"])), bound
+
+
 def decode_tape_fragments(hdr, rows, tap_path, spans, opts: DecodeOptions | None = None, fe_factory=None, halo_rows=1 << 16, cfgkw=None,
                           peakstats: bool = False):
     """Decodes one resident tape as the fragments `spans` = [(lo, hi), ...] (contiguous, cuts on the 64-row grid), one after the other
@@ -637,25 +661,9 @@ def decode_tape_fragments(hdr, rows, tap_path, spans, opts: DecodeOptions | None
     full = default_parmsets(hdr.mode, opts.nparmsets or (15 if opts.multiple_tries else 1))
     cfg = frontend.FrontEndConfig.from_header(hdr, parmsets=frontend_parmsets(full), **(cfgkw or {}))
     fe = (fe_factory or frontend.FrontEnd)(cfg)
-    n = int(rows.shape[0])
     out, total = [], 0
     with open(tap_path, "wb") as tapf:
-        for k, (lo, hi) in enumerate(spans):
-            if hi <= lo:
-                continue
-            is_last = hi >= n
-            halo = halo_rows
-            while True:
-                end = n if is_last else min(n, hi + halo)
-                piece = rows[lo:end]
-                res, nb, bound = scan_fragment(fe, piece, hi - lo, lo, lo == 0, is_last)()
-                if nb is not None or end >= n:
-                    break
-                halo *= 4                                   # the last own burst runs past the halo: ask the neighbour for more
-            # (nb None with the halo at the end of the tape: no further zone exists, the last own burst runs to the end of the data)
-            if res.nbursts == 0:
-                continue
-            start = 0 if lo == 0 else int(res.bursts[0]["zone_first"])
+        for k, lo, hi, piece, res, start, bound in scan_spans(fe, rows, spans, halo_rows):
             frag = tap_path + f".frag{k}"
             st = decode_fragment(hdr, cfg, fe, res, piece, lo, start, bound, frag, full, opts, fe_factory)
             data = open(frag, "rb").read()
@@ -668,3 +676,283 @@ def decode_tape_fragments(hdr, rows, tap_path, spans, opts: DecodeOptions | None
             tapf.write(b"\xff\xff\xff\xff")                 # src/readtape.c:1885
     fe.close()
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Windows: fragments that decode side by side and ONE finisher that puts the blocks out.  A fragment's replay in journal mode
+# writes nothing; its blocks go into a journal (librtdecode.so: rt_replay_journal_fragments), and the finisher - the resident decode's own output
+# stage around one context - takes the journals in tape order: block and file numbers, labels, the text file, -blklimit, the summary and the peak
+# statistics come out as the resident decode's.
+# ---------------------------------------------------------------------------------------------------------------------
+WORK_COUNTERS = ("attempts", "exact_scans", "chained", "events_delivered", "agc_mismatches")      # the replay's own: what the fragments' replays did, summed
+
+
+def _journal_api(lib):
+    if getattr(lib, "_journal_api", False):
+        return lib
+    lib.rt_peakbins_new.restype = C.c_void_p
+    lib.rt_peakbins_free.argtypes = [C.c_void_p]
+    lib.rt_journal_new.restype = C.c_void_p
+    lib.rt_journal_new.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    lib.rt_journal_free.argtypes = [C.c_void_p]
+    lib.rt_journal_bytes.restype = C.c_int64
+    lib.rt_journal_bytes.argtypes = [C.c_void_p]
+    lib.rt_journal_records.argtypes = [C.c_void_p]
+    lib.rt_journal_stats.argtypes = [C.c_void_p, C.POINTER(_Stats)]
+    lib.rt_journal_final_row.restype = C.c_int64
+    lib.rt_journal_final_row.argtypes = [C.c_void_p]
+    lib.rt_replay_journal_fragments.argtypes = lib.rt_replay_run.argtypes[:15] + [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double)]
+    lib.rt_journal_finisher_new.restype = C.c_void_p
+    lib.rt_journal_finisher_new.argtypes = [C.POINTER(_Options), C.POINTER(_Parms), C.c_int, C.c_int64, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_void_p]
+    lib.rt_journal_finish.argtypes = [C.c_void_p, C.c_void_p]
+    lib.rt_journal_finisher_end.argtypes = [C.c_void_p, C.POINTER(_Stats), C.POINTER(C.c_double)]
+    lib._journal_api = True
+    return lib
+
+
+def _decoder_options(hdr, cfg, opts, tap_format=True):
+    return _Options(mode=hdr.mode, ntrks=hdr.ntrks, bpi=cfg.bpi, ips=cfg.ips, specified_parity=0 if opts.even_parity else 1,
+                    revparity=opts.revparity, do_correction=int(opts.correct), find_zeros=int(cfg.find_zeros), do_differentiate=int(cfg.differentiate),
+                    multiple_tries=int(opts.multiple_tries), tap_format=int(tap_format), add_parity=int(opts.add_parity), verbose=int(opts.verbose))
+
+
+def journal_fragments(hdr, cfg, fe, res, rows_with_halo, lo, start_rows, stop_rows, journals, full, opts, fe_factory=None, exact_lock=None):
+    """decode_fragments in journal mode: the fragments of ONE scan side by side on native threads, each into its journal (Finisher.journal), nothing written.
+    Returns each fragment's seconds.  A fragment that met one of the reference's fatal asserts, or that the device could not serve, raises as decode_tape does."""
+    from readtape_amd import shard
+    lib = _journal_api(_load_decode_lib())
+    o = _decoder_options(hdr, cfg, opts)
+    parr = (_Parms * len(full))(*full)
+    W = (C.c_int * len(full))(*fe.widths)
+    exact, free, keep = _exact_callbacks(fe, rows_with_halo, hdr.ntrks, fe_factory, lock=exact_lock)
+    n = len(journals)
+    secs = (C.c_double * n)()
+    js = (C.c_void_p * n)(*journals)
+    starts = (C.c_int64 * n)(*[int(a) for a in start_rows])
+    stops = (C.c_int64 * n)(*[I64MAX if b is None else int(b) for b in stop_rows])
+    bursts = np.ascontiguousarray(shard.absolute_bursts(res, lo))
+    counts = np.ascontiguousarray(res.counts)
+    rc = lib.rt_replay_journal_fragments(C.byref(o), parr, len(full), hdr.tdelta_ns, hdr.tstart_ns, int(rows_with_halo.shape[0]), lo, W,
+                                         bursts.ctypes.data, len(bursts), counts.ctypes.data, res._events.ctypes.data, exact, free, None,
+                                         n, js, starts, stops, secs)
+    _release(keep)
+    if rc != 0:
+        raise RuntimeError("rt_replay_journal_fragments failed")
+    return [float(s) for s in secs]
+
+
+class Finisher:
+    """The ordered end of a windowed decode, on the thread that makes it: takes the requests of a resident run (text file, labels, block limit, peak
+    statistics), makes the fragments' journals, is given them back in tape order (`finish`, True once the block limit is reached: nothing behind it is
+    wanted) and ends the run (`end` -> the resident decode's statistics)."""
+
+    def __init__(self, hdr, cfg, full, opts, tap_path=None, log_path=None, out_base=None, in_name=None, tap_format=True, labels=False, blklimit=None,
+                 textfile=None, created=None, peak_base=None, quiet=False, append=False):
+        self.lib = lib = _journal_api(_load_decode_lib())
+        self.ntrks, self.quiet, self.peak_base = hdr.ntrks, quiet, peak_base
+        self.bins = lib.rt_peakbins_new() if peak_base is not None else None
+        self.snapshots = int(blklimit is not None)
+        self.made, self.limited, self.h, self.final_row = 0, False, None, 0
+        _request_text(lib, textfile, out_base, tap_path, created)
+        _request_run(lib, labels, blklimit)
+        o = _decoder_options(hdr, cfg, opts, tap_format)
+        parr = (_Parms * len(full))(*full)
+        summary = (in_name or out_base + ".tbin") if out_base else None
+        self.h = lib.rt_journal_finisher_new(C.byref(o), parr, len(full), hdr.tdelta_ns, tap_path.encode() if tap_path and not out_base else None,
+                                             out_base.encode() if out_base else None, summary.encode() if summary else None,
+                                             log_path.encode() if log_path else None, int(append), self.bins)
+        lib.rt_driver_set_run(0, -1)
+        if not self.h:
+            raise RuntimeError("rt_journal_finisher_new failed")
+
+    def journal(self, first=None):
+        """a journal for the next fragment made (first: it is the tape's first fragment - by default the first one asked for)"""
+        first = (self.made == 0) if first is None else first
+        self.made += 1
+        return self.lib.rt_journal_new(self.bins, int(bool(first)), self.snapshots)
+
+    def overrun(self, first_safe_last):
+        """Whether the fragment in front ended BEHIND the rows from which the next fragment's first attempt may start (first_safe_last: the absolute
+        safe_last of that fragment's first burst): its last block ran into the next fragment's first zone and past the proven restart - the resident decode
+        goes on from where that block ended, so the next fragment must be replayed again from self.final_row (rare: a block whose end was found late)."""
+        return self.final_row > int(first_safe_last)
+
+    def finish(self, journal):
+        """the next journal in tape order; it is freed.  -> (records, bytes, the fragment's own replay counters: WORK_COUNTERS) it held"""
+        if not self.limited:                                  # (never backwards: a fragment replayed again from a row behind its own stop ends at that stop)
+            self.final_row = max(self.final_row, int(self.lib.rt_journal_final_row(journal)))
+        st = _Stats()
+        self.lib.rt_journal_stats(journal, C.byref(st))
+        info = (int(self.lib.rt_journal_records(journal)), int(self.lib.rt_journal_bytes(journal)), {k: int(getattr(st, k)) for k in WORK_COUNTERS})
+        rc = 1 if self.limited else self.lib.rt_journal_finish(self.h, journal)
+        self.lib.rt_journal_free(journal)
+        if rc < 0:
+            raise RuntimeError("rt_journal_finish: not a finished journal")
+        self.limited = self.limited or rc == 1
+        return info
+
+    def discard(self, journal):
+        self.lib.rt_journal_free(journal)
+
+    def end(self):
+        st, secs = _Stats(), C.c_double(0)
+        h, self.h = self.h, None
+        try:
+            rc = self.lib.rt_journal_finisher_end(h, C.byref(st), C.byref(secs)) if h else -1
+        finally:
+            peaks = _collect_peakstats(self.lib, self.peak_base, self.ntrks, self.quiet)
+            if self.bins:
+                self.lib.rt_peakbins_free(self.bins)
+                self.bins = None
+        if rc != 0:
+            raise RuntimeError("rt_journal_finisher_end failed")
+        stats = {k: getattr(st, k) for k, _ in _Stats._fields_}
+        stats.update(peaks)
+        stats["finisher_seconds"] = float(secs.value)
+        if stats["reference_fatal"]:
+            raise ReferenceFatal(f"AGC gain bad in lookfor_peak on track {stats['fatal_trk']} at sample {stats['fatal_row']}: the reference asserts and exits "
+                                 "here (src/decoder.c:782)", stats)
+        if stats["device_failures"]:
+            raise RuntimeError(f"the device front end could not deliver {stats['device_failures']} attempt(s): the decode is incomplete")
+        return stats
+
+    def abandon(self):
+        """a run that ends early (an exception on the way): the files are closed, the requests taken back"""
+        if self.h:
+            try:
+                self.end()
+            except Exception:
+                pass
+
+
+def settle_prepasses(hdr, rows, full, opts, cfgkw, deskew, fe_factory, log_path, prefix_rows=1 << 22):
+    """The resident decode's two pre-passes (decode_tape) for a decode configured by cfgkw: the density of a header without one, then the -deskew delays
+    unless cfgkw names them or the mode is PE - both continue `log_path`.  -> (cfgkw with "bpi" / "skew", whether the log has been begun)"""
+    cfgkw = dict(cfgkw or {})
+    det = {k: bool(cfgkw.get(k, False)) for k in ("invert", "find_zeros", "differentiate")}
+    began = False
+
+    def probe(bpi):
+        return _Options(mode=hdr.mode, ntrks=hdr.ntrks, bpi=bpi, ips=hdr.ips or 50.0, specified_parity=0 if opts.even_parity else 1,
+                        revparity=opts.revparity, do_correction=int(opts.correct), find_zeros=int(det["find_zeros"]), do_differentiate=int(det["differentiate"]),
+                        multiple_tries=int(opts.multiple_tries), tap_format=1, add_parity=int(opts.add_parity), verbose=int(opts.verbose))
+
+    if hdr.mode != tbin.MODE_GCR and not hdr.bpi > 0 and not cfgkw.get("bpi"):
+        cfgkw["bpi"] = detect_density(hdr, rows, full, probe(0.0), fe_factory, invert=det["invert"], log_path=log_path, first_prefix_rows=prefix_rows)
+        began = True
+    if deskew and cfgkw.get("skew") is None and hdr.mode != tbin.MODE_PE:
+        bpi_kw = {"bpi": cfgkw["bpi"]} if cfgkw.get("bpi") else {}
+        cfg0 = frontend.FrontEndConfig.from_header(hdr, **bpi_kw)
+        rest = {k: v for k, v in cfgkw.items() if k not in ("invert", "find_zeros", "differentiate", "skew")}
+        o = probe(cfg0.bpi)
+        o.ips = cfg0.ips
+        cfgkw["skew"] = calibrate_deskew(hdr, rows, full, o, fe_factory, log_path=log_path, first_prefix_rows=prefix_rows, append=began, **det, **rest)
+        began = began or log_path is not None
+    return cfgkw, began
+
+
+def decode_tape_windows(hdr, rows, spans, tap_path=None, log_path=None, out_base=None, in_name=None, tap_format=True, opts: DecodeOptions | None = None,
+                        labels=False, blklimit=None, textfile=None, created=None, peakstats=False, quiet=False, fe_factory=None, halo_rows=1 << 16,
+                        cfgkw=None, threads=1, parms_text=None, deskew=False, replay_order=None):
+    """decode_tape's outputs from decode_tape_fragments' decode: the resident tape is scanned as the fragments `spans` = [(lo, hi), ...] (contiguous, cuts
+    on the 64-row grid), the fragments' replays journal their blocks - `threads` of them side by side -, and one finisher puts the journals out in tape
+    order: tap_path, or out_base's files by the reference's names (<out_base>.tap, the numbered or label-named .bin files), the log with its summary
+    (in_name), the text file, labels, blklimit, peakstats / quiet exactly as decode_tape's arguments of those names.  cfgkw: the front end's configuration
+    (skew, invert, find_zeros, differentiate, bpi); parms_text: a .parms text; deskew: calibrate the delays first.  replay_order(indices) -> the order in which
+    the fragments' replays are started (default: tape order; the outputs do not depend on it).
+    Returns the statistics of decode_tape (blocks, tapemarks, all_ok ..., peakstats / skew_ok where asked for, bursts, skew, bpi) with "spans": a dict per
+    fragment (span, records, journal_bytes, seconds and its replay's own counters), and "finisher_seconds".  The replay's counters in the statistics
+    (WORK_COUNTERS) are the fragments' sums; with one span they are the resident decode's."""
+    import threading
+    from concurrent.futures import ThreadPoolExecutor
+    opts = opts or DecodeOptions()
+    if hdr.mode == tbin.MODE_WW:
+        raise NotImplementedError("Whirlwind tapes are one chain (no independent fragments): use decode_tape")
+    if opts.add_parity and hdr.ntrks >= 9:
+        raise ValueError(f"-addparity is not allowed with ntrks={hdr.ntrks}")
+    lib = _load_decode_lib()
+    nsets = opts.nparmsets or (15 if opts.multiple_tries else 1)
+    if parms_text:
+        arr = (_Parms * 15)()
+        n = lib.rt_parse_parms_text(hdr.mode, parms_text.encode(), arr)
+        if n <= 0:
+            raise ValueError("bad .parms text")
+        full = [arr[i] for i in range(n)][:nsets]
+    else:
+        full = default_parmsets(hdr.mode, nsets)
+    given_skew = (cfgkw or {}).get("skew") is not None
+    peak_base = _request_peakstats(lib, peakstats, out_base, tap_path, quiet, bool(deskew) or given_skew)
+    fin = fe = fe_exact = pool = None
+    journals = {}
+    try:
+        cfgkw, began = settle_prepasses(hdr, rows, full, opts, cfgkw, deskew, fe_factory, log_path)
+        cfg = frontend.FrontEndConfig.from_header(hdr, parmsets=frontend_parmsets(full), **cfgkw)
+        fin = Finisher(hdr, cfg, full, opts, tap_path=tap_path, log_path=log_path, out_base=out_base, in_name=in_name, tap_format=tap_format, labels=labels,
+                       blklimit=blklimit, textfile=textfile, created=created, peak_base=peak_base, quiet=quiet, append=began)
+        make = fe_factory or frontend.FrontEnd
+        fe = make(cfg)
+        threads = max(1, int(threads))
+        fe_exact, lock = (make(cfg), threading.Lock()) if threads > 1 else (fe, None)      # (exact rescans of replays that run beside the scans: their own context, one at a time)
+        frags = []
+        for k, lo, hi, piece, res, start, bound in scan_spans(fe, rows, spans, halo_rows):
+            frags.append((lo, hi, piece, res.detach(), start, bound))      # (the next scan reuses the context's buffers)
+        info, redone, nbursts = [None] * len(frags), 0, 0
+        for i in range(len(frags)):
+            journals[i] = fin.journal(first=(i == 0))
+
+        def replay(i):
+            lo, hi, piece, res, start, bound = frags[i]
+            secs = journal_fragments(hdr, cfg, fe_exact, res, piece, lo, [start], [bound], [journals[i]], full, opts, fe_factory, exact_lock=lock)
+            return secs[0]
+
+        order = list(replay_order(list(range(len(frags)))) if replay_order else range(len(frags)))
+        assert sorted(order) == list(range(len(frags)))
+        in_order = order == list(range(len(frags)))
+        if threads > 1:
+            pool = ThreadPoolExecutor(threads)
+            futs = {i: pool.submit(replay, i) for i in order}
+            secs = lambda i: futs[i].result()
+        elif in_order:
+            secs = replay                                         # (tape order on this thread: every journal is finished, and freed, as soon as it is written)
+        else:
+            done = {i: replay(i) for i in order}
+            secs = lambda i: done[i]
+        for i in range(len(frags)):
+            if fin.limited:
+                if threads > 1:
+                    futs[i].cancel() or futs[i].result()
+                fin.discard(journals.pop(i))
+                nbursts += frags[i][3].nbursts
+                continue
+            s = secs(i)
+            lo, hi, piece, res, start, bound = frags[i]
+            if i > 0 and fin.overrun(lo + int(res.bursts[0]["safe_last"])):
+                fin.discard(journals.pop(i))                      # the block in front ended inside this fragment's first zone: again, from there
+                journals[i] = fin.journal(first=False)
+                s += journal_fragments(hdr, cfg, fe_exact, res, piece, lo, [fin.final_row - lo], [bound], [journals[i]], full, opts, fe_factory, exact_lock=lock)[0]
+                redone += 1
+            records, nbytes, work = fin.finish(journals.pop(i))
+            info[i] = dict(span=(lo, hi), records=records, journal_bytes=nbytes, seconds=s, **work)
+            nbursts += res.nbursts
+            frags[i] = piece = res = None                         # (its rows and its scan are not needed any more)
+        f, fin = fin, None
+        stats = f.end()
+    finally:
+        if pool:
+            pool.shutdown(wait=True, cancel_futures=True)
+        if fin is not None:
+            fin.abandon()
+        elif peak_base is not None:
+            lib.rt_replay_set_peakstats(None, 0, 0)
+        for j in journals.values():
+            lib.rt_journal_free(j)
+        if fe_exact is not None and fe_exact is not fe:
+            fe_exact.close()
+        if fe is not None:
+            fe.close()
+    stats["bursts"] = nbursts
+    stats["skew"] = list(cfg.skew) if cfg.skew is not None else None
+    stats["bpi"] = cfg.bpi
+    stats["spans"] = [x for x in info if x is not None]
+    stats["fragments_redone"] = redone
+    return stats
