@@ -449,6 +449,51 @@ size_t rtfe_text_format_scratch_bytes(const rtfe_text_item *items, int64_t nitem
 int    rtfe_text_format(const void *d_image, uint64_t image_bytes, const rtfe_text_item *items, const rtfe_text_item *d_items, int64_t nitems, uint64_t nlinefeeds,
                         const rtfe_text_options *o, void *d_text, size_t text_cap, void *d_scratch, size_t scratch_bytes, rtfe_text_out *d_out, void *stream);
 
+/* ---- the tape writer: flux transitions -> the int16 rows a head would have read, rendered on the device.  Handle-free.
+ * The other direction of everything above.  The host encoder (rt_tapewrite_encode / rt_tapewrite_raw, csrc/host/rt_tapewrite.h) turns a SIMH .tap image into
+ * a SLOT STREAM and a BLOCK TABLE; rtfe_tape_render turns a window of the tape they describe into rows, byte for byte what the host renderer
+ * rt_tapewrite_render gives.  Queued on `stream`, no allocation, no host synchronisation.  The ABI version did not move: additions only, and
+ * rtfe_kernel_count() stays what it was (this kernel is no span of a scan).
+ *
+ * The model (csrc/host/rt_tapewrite_model.h holds it as code, shared by the host renderer and the kernel):
+ *   A slot is a place where flux may change: bit t of `flux` = track t has a transition there, bit t of `neg` = that transition reads as a negative pulse.
+ *   Slot s of a block lies at cell position s * pitch, pitch = 1 (pitch_shift 0: NRZI, GCR) or 1/2 cell (pitch_shift 1: PE).  A block of the table owns
+ *   rows [first_row, first_row + rows) of the tape and slots [first_slot, first_slot + nslots) of the stream; blocks are sorted and do not overlap; rows
+ *   that belong to no block are gap.  With r the row counted from the block's first, a transition of track t in slot s has
+ *      c = (8 + s * pitch + 0.5 + skew[t] + jit) * spb,   jit = g(jkey[t], first_slot + s) * jitter          (0 where jitter == 0)
+ *   and adds  a * (1 / (1 + d * d) - edge),  d = (r - c) / w,  a = +-amp[t], to every row of ITS OWN block with |r - rint(c)| <= K.  A sample is the sum of
+ *   these from 0.0 in ascending slot order, plus g(nkey[t], row of the tape) * noise_mv * 1e-3 (where noise_mv > 0, in gaps too), quantised
+ *   rint(v / maxvolts * 32767) and clipped to +-32767.  Every operation is an IEEE double + - * / or rint in the order written, no FMA, no libm.
+ *   g(key, n): z = key + n * 0x9E3779B97F4A7C15, the splitmix64 finaliser over z, its four 16-bit fields summed (Irwin-Hall), minus 131070, times
+ *   0x1.bb67ae86627e8p-16 (one over the sum's standard deviation): mean 0, variance 1, close to normal, and BOUNDED: |g| <= 3.4641.  A function of the
+ *   absolute row / slot, so a window of a tape is the same slice of the whole.  rt_tapewrite_params fills the structure from a physical description.
+ *
+ * rtfe_tape_render: rows [first_row, first_row + nrows) of the tape into d_rows[0 .. nrows * ntrks).  `blocks` (host) and d_blocks (device) are the same
+ *   table; the host copy is checked, the kernel reads the device copy.  d_slots: the whole stream, device.  p: host.
+ * Memory contract: reads d_slots[0 .. nslots) and d_blocks[0 .. nblocks); writes exactly the bytes of d_rows[0 .. nrows * ntrks) - none in front, none
+ *   behind: a workgroup takes a span of rtfe_tape_render_span_rows(ntrks) rows ON THE TAPE'S OWN GRID (row 0 of the tape starts a span, whatever the
+ *   window), stages its samples in LDS and stores whole aligned 16-byte vectors; the partial vectors at a span's ends - at the window's two ends, and where
+ *   a span's bytes are no multiple of 16 - are stored sample by sample.
+ * Refusals, all before anything is queued (d_rows is left alone): a null pointer (d_slots and the block tables may be null when their count is 0): -1;
+ *   p->ntrks outside 1 .. 19: -3; d_rows not 16-byte aligned: -31; a negative count or row, or more rows than a launch takes: -34; a parameter that is
+ *   no finite number where the model needs one, maxvolts or spb or w not above 0, pitch_shift outside 0 .. 1: -62; a block table that is not sorted, overlaps,
+ *   has a negative field, names slots outside [0, nslots) or more than 2^31 - 1 slots in a block: -61; a reach K outside 0 .. RTFE_TAPE_MAX_REACH, or a
+ *   slot pitch so fine (spb * pitch rows a slot) that the slots one span needs - (span rows + 2 * (K + 2 + ceil((max |skew| + 3.4641 jitter) * spb))) /
+ *   (spb * pitch) + 7 - exceed the RTFE_TAPE_MAX_SLOTS the kernel stages: -60.  rtfe_last_error says which. */
+#define RTFE_TAPE_MAX_REACH 2048
+#define RTFE_TAPE_MAX_SLOTS 2048
+typedef struct rtfe_tape_slot { uint32_t flux, neg; } rtfe_tape_slot;                                    /* 8 bytes */
+typedef struct rtfe_tape_block { int64_t first_row, rows, first_slot, nslots; } rtfe_tape_block;        /* 32 bytes */
+typedef struct rtfe_tape_params {
+   int32_t ntrks, pitch_shift, K, reserved;
+   double spb, w, edge, maxvolts, noise_mv, jitter;      /* rows a cell; the pulse's half width in rows; 1 / (1 + (K / w)^2); ...; sigma in cells */
+   double amp[19], skew[19];                              /* volts; cells */
+   uint64_t nkey[19], jkey[19];                           /* the generator's keys: noise by row, jitter by slot */
+} rtfe_tape_params;
+int64_t rtfe_tape_render_span_rows(int ntrks);                  /* rows one workgroup takes: for tests and tools that aim at its seams */
+int rtfe_tape_render(const rtfe_tape_slot *d_slots, int64_t nslots, const rtfe_tape_block *blocks, const rtfe_tape_block *d_blocks, int64_t nblocks,
+                     const rtfe_tape_params *p, int64_t first_row, int64_t nrows, int16_t *d_rows, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

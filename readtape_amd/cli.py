@@ -11,7 +11,7 @@ for the base name, and which header field or option wins, follows src/readtape.c
   find_parms(base, mode) / parms_options(text)             the parameter-set file of a run and the `readtape` lines in it
 
 One decode is one call of pipeline.decode_tape (ingest.decode_file_streaming with --stream, textfile.write_text[_device] with -tapread); a list run
-(-f) decodes its files one after the other in this process."""
+(-f) decodes its files one after the other in this process.  --write goes the other way: tapewrite.write_tbin[_device] renders a .tap image as a .tbin."""
 from __future__ import annotations
 
 import dataclasses
@@ -104,6 +104,11 @@ options:
                  say under the summary whether the head skew is significant (-q: only the
                  -deskew file, as in readtape; every file of a -f list gets its own; not with
                  --stream, whose windows do not share the bins the first transition fixes)
+  --write[=host] the other direction: render the SIMH file <basefilename>[.tap] as the analog
+                 <basefilename>.tbin a head would have read, on the device [=host: on the host,
+                 the same bytes].  Give the format: -nrzi (-ntrks=7 or 9, -even), -pe or -gcr;
+                 -bpi= -ips= -outf= -outp= as above; --tdelta=ns the sample time, --noise=mV,
+                 --jitter=cells, --seed=n, --gap=samples between blocks.  Whirlwind is not written.
 
 not built (the run ends with status 2): -showibg=n -sumt=sss -sumc=ccc -adjskew -d[n]
   <basefilename>.peakstats.csv is not written unless --peakstats is given: gathering it puts
@@ -171,6 +176,12 @@ class Options:
     stream: bool = False
     windows: int | None = None         # --windows[=rows]: None not given, 0 the window --stream computes
     peakstats: bool = False
+    write: str | None = None           # --write[=host]: "device" / "host"
+    tdelta: int | None = None          # --tdelta= ... --gap=: the writer's; None: the format's default
+    noise: float | None = None
+    jitter: float | None = None
+    seed: int | None = None
+    gap: int | None = None
 
     def text_options(self):
         """-textfile's options as the run uses them (src/readtape.c:1940-1946): any number or character type asks for the file; 32 characters a line
@@ -328,6 +339,19 @@ def parse_option(o: Options, option: str) -> bool:
     if up == "-WINDOWS":
         o.windows = 0
         return True
+    if up in ("-WRITE", "-WRITE=HOST"):
+        o.write = "host" if up.endswith("HOST") else "device"
+        return True
+    for kw, name, lo, hi in (("-TDELTA=", "tdelta", 1, 10_000_000), ("-SEED=", "seed", 0, INT_MAX), ("-GAP=", "gap", 0, INT_MAX)):
+        ok, n = _int(arg, kw, lo, hi)
+        if ok:
+            setattr(o, name, n)
+            return True
+    for kw, name, hi in (("-NOISE=", "noise", 1e6), ("-JITTER=", "jitter", 1.0)):
+        ok, x = _float(arg, kw, 0.0, hi)
+        if ok:
+            setattr(o, name, x)
+            return True
     ok, n = _int(arg, "-WINDOWS=", 1024, 1 << 30)
     if ok:
         o.windows = -(-n // 1024) * 1024                      # (windows are cut on the 1024-row grid)
@@ -668,7 +692,41 @@ def tapread(o: Options, base, ext, out_base, fe_factory, out):
     _say(out, o, f"created {r['name']}\n")
 
 
-def run(argv, fe_factory, out):
+def write_tape(o: Options, argv, base, ext, out_base, device, out):
+    """--write: <base>[.tap] -> <out_base>.tbin (tapewrite.write_tbin / write_tbin_device).  A combination the writer does not take ends with status 2."""
+    from . import tapewrite as tw, textfile as tf
+    given = [a.upper() for a in argv if a.upper() in ("-NRZI", "-PE", "-GCR", "-WHIRLWIND")]
+    why = ("--write does not write Whirlwind tapes: a Whirlwind pulse is two transitions 0.35 cell apart, off the writer's half-cell grid" if "-WHIRLWIND" in given else
+           "--write wants the tape's format: -nrzi, -pe or -gcr" if not given else
+           "--write renders a .tap image: leave --stream, --windows, -tapread and -f out" if (o.stream or o.windows is not None or o.tap_read or o.filelist) else
+           f"--write reads a SIMH .tap file, not {ext}" if ext.lower() not in ("", ".tap") else None)
+    if why:
+        raise CliExit(2, why + "\n")
+    kw = {k: v for k, v in (("tdelta_ns", o.tdelta), ("noise_mv", o.noise), ("jitter", o.jitter), ("gap_samples", o.gap)) if v is not None}
+    seed = 1 if o.seed is None else o.seed
+    spec = (tw.nrzi_spec(seed=seed, ntrks=o.ntrks_specified or 9, even=o.even_parity, **kw) if o.mode == tbin.MODE_NRZI else
+            (tw.pe_spec if o.mode == tbin.MODE_PE else tw.gcr_spec)(seed=seed, ntrks=o.ntrks_specified or 9, even=o.even_parity, **kw))
+    if o.bpi_specified >= 0:
+        spec.bpi = o.bpi_specified
+    if o.ips_specified >= 0:
+        spec.ips = o.ips_specified
+    path = base + (ext or ".tap")
+    if not os.path.isfile(path):
+        raise fatal(f"Unable to open SIMH TAP file \"{path}\"")
+    _say(out, o, f"rendering {path}\n")
+    try:
+        if o.write == "host":
+            r = tw.write_tbin(path, out_base + ".tbin", spec)
+        else:
+            r = tw.write_tbin_device(path, out_base + ".tbin", spec, **({} if device is None else dict(_lib_path=device[0], _backend=device[1])))
+    except tw.TapeWriteError as e:
+        raise CliExit(2, f"--write: {e}\n")
+    except tf.TapFormatError as e:
+        raise fatal(str(e))
+    _say(out, o, f"created {out_base}.tbin: {r['rows']} samples, {r['blocks']} blocks\n")
+
+
+def run(argv, fe_factory, out, device=None):
     if not argv:
         raise CliExit(4, "", usage=True)
     o, rest = parse_args(argv)
@@ -685,6 +743,9 @@ def run(argv, fe_factory, out):
             return o.outf
         return o.outp + b
 
+    if o.write:
+        write_tape(o, argv, base, ext, outbase_of(base), device, out)
+        return 0
     if o.tap_read or ext.lower() == ".tap":
         if o.stream:
             raise CliExit(2, "--stream decodes a .tbin file, -tapread reads a .tap\n")
@@ -715,13 +776,13 @@ def run(argv, fe_factory, out):
     return 0
 
 
-def main(argv=None, *, fe_factory=None, out=None) -> int:
+def main(argv=None, *, fe_factory=None, out=None, device=None) -> int:
     """Runs one command line; returns the exit status.  fe_factory: pipeline.decode_tape's (the tests pass the emulated front end); out: where the console
-    text goes (sys.stdout)."""
+    text goes (sys.stdout); device: --write's (front-end library path, backend), for the same tests."""
     argv = list(sys.argv[1:] if argv is None else argv)
     out = out or sys.stdout
     try:
-        return run(argv, fe_factory, out)
+        return run(argv, fe_factory, out, device)
     except CliExit as e:
         if e.message:
             sys.stderr.write(e.message)

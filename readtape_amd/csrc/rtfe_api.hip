@@ -26,6 +26,7 @@
 #include "rtfe_csv.hip"
 #include "rtfe_csvout.hip"
 #include "rtfe_textfile.hip"
+#include "rtfe_tapewrite.hip"
 
 namespace rtfe {
 __global__ void k_setup_exact(rtfe_burst *burst, BurstScratch *scratch, long long reset_row, long long end_row,
@@ -1354,3 +1355,43 @@ extern "C" int rtfe_text_format(const void *d_image, uint64_t image_bytes, const
                       k.out_bytes, (unsigned long long)text_cap, k.out_flags, (uint32_t)RTFE_TEXT_FULL);
    hipLaunchKernelGGL(k_tx_format, dim3(grid), dim3(kTxWave), 0, st, k);
    return launch_check("rtfe_text_format"); }
+
+// ---- a slot stream and a block table -> the tape's rows on the device (include/rt_frontend.h; the kernel is rtfe_tapewrite.hip) ----
+extern "C" int64_t rtfe_tape_render_span_rows(int ntrks) { return ntrks >= 1 && ntrks <= RTFE_MAXTRKS ? kTwSpanRows : 0; }
+
+extern "C" int rtfe_tape_render(const rtfe_tape_slot *d_slots, int64_t nslots, const rtfe_tape_block *blocks, const rtfe_tape_block *d_blocks, int64_t nblocks,
+                                const rtfe_tape_params *p, int64_t first_row, int64_t nrows, int16_t *d_rows, void *stream) {
+   if (!p || !d_rows) return fail(-1, "rtfe_tape_render: null argument");
+   if (nslots < 0 || nblocks < 0 || first_row < 0 || nrows < 0 || first_row > INT64_MAX - nrows) return fail(-34, "rtfe_tape_render: a negative count or row (nslots %lld, nblocks %lld, first_row %lld, nrows %lld)", (long long)nslots, (long long)nblocks, (long long)first_row, (long long)nrows);
+   if ((nslots > 0 && !d_slots) || (nblocks > 0 && (!blocks || !d_blocks))) return fail(-1, "rtfe_tape_render: null argument");
+   if (p->ntrks < 1 || p->ntrks > RTFE_MAXTRKS) return fail(-3, "rtfe_tape_render: ntrks %d out of range", p->ntrks);
+   if (((uintptr_t)d_rows & 15) != 0) return fail(-31, "rtfe_tape_render: d_rows must be 16-byte aligned");
+   if (!(p->spb > 0 && std::isfinite(p->spb)) || !(p->w > 0 && std::isfinite(p->w)) || !std::isfinite(p->edge) || !(p->maxvolts > 0 && std::isfinite(p->maxvolts)) ||
+       !(p->noise_mv >= 0 && std::isfinite(p->noise_mv)) || !(p->jitter >= 0 && std::isfinite(p->jitter)) || p->pitch_shift < 0 || p->pitch_shift > 1)
+      return fail(-62, "rtfe_tape_render: spb %g, w %g, edge %g, maxvolts %g, noise %g mV, jitter %g, pitch shift %d: not a tape", p->spb, p->w, p->edge, p->maxvolts, p->noise_mv, p->jitter, p->pitch_shift);
+   double skew = 0;
+   for (int t = 0; t < p->ntrks; ++t) {
+      if (!std::isfinite(p->amp[t]) || !std::isfinite(p->skew[t])) return fail(-62, "rtfe_tape_render: track %d: amplitude %g, skew %g", t, p->amp[t], p->skew[t]);
+      if (fabs(p->skew[t]) > skew) skew = fabs(p->skew[t]); }
+   if (p->K < 0 || p->K > RTFE_TAPE_MAX_REACH) return fail(-60, "rtfe_tape_render: a reach of %d rows (0 .. %d)", p->K, RTFE_TAPE_MAX_REACH);
+   TapeArgs k;
+   const double astray = ceil((skew + RT_TW_GMAX * p->jitter) * p->spb);                 // rows a transition can lie from its slot's nominal place
+   k.slots_per_row = 1.0 / (p->spb * (p->pitch_shift ? 0.5 : 1.0));
+   const double need = (kTwSpanRows + 2.0 * (p->K + 2.0 + astray)) * k.slots_per_row + 7.0;
+   if (!(need <= kTwSlotCap)) return fail(-60, "rtfe_tape_render: %.3f rows a slot with a reach of %d rows and %.0f of skew and jitter: a span needs %.0f slots, the kernel stages %d", 1.0 / k.slots_per_row, p->K, astray, need, kTwSlotCap);
+   int64_t row = 0;
+   for (int64_t b = 0; b < nblocks; ++b) {
+      const rtfe_tape_block &B = blocks[b];
+      if (B.first_row < row || B.rows < 1 || B.rows > INT64_MAX - B.first_row || B.first_slot < 0 || B.nslots < 0 || B.nslots > 0x7fffffffll || B.first_slot > nslots || B.nslots > nslots - B.first_slot)
+         return fail(-61, "rtfe_tape_render: block %lld of the table (rows %lld + %lld, slots %lld + %lld of %lld) is out of order or out of range", (long long)b, (long long)B.first_row, (long long)B.rows, (long long)B.first_slot, (long long)B.nslots, (long long)nslots);
+      row = B.first_row + B.rows; }
+   if (nrows == 0) return 0;
+   k.span0 = first_row / kTwSpanRows;
+   const int64_t nwg = (first_row + nrows - 1) / kTwSpanRows - k.span0 + 1;
+   if (nwg > 0x7fffffffll) return fail(-34, "rtfe_tape_render: %lld rows are more than a launch takes", (long long)nrows);
+   k.slots = d_slots; k.blocks = d_blocks; k.nblocks = nblocks; k.first_row = first_row; k.nrows = nrows; k.rows = d_rows;
+   k.reach = (long long)(p->K + 2 + astray);
+   k.lead_rows = (RT_TW_LEAD + 0.5) * p->spb;
+   k.p = *p;
+   hipLaunchKernelGGL(k_tape_render, dim3((unsigned)nwg), dim3(kTwThreads), 0, (hipStream_t)stream, k);
+   return launch_check("rtfe_tape_render"); }
